@@ -16,8 +16,19 @@ scene already resident in HBM; the image's 8x8 tiles are interleaved over
 the ranks (tile T -> rank T % N), and for N > 1 the ranks' packed tiles are
 gathered to rank 0 over RCCL and un-interleaved there inside the step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the headline line
+(with the roofline of those very steps: their counters and kernel times, no
+run of its own).  `--full` adds what takes runs of its own after the timed
+region, on one GPU: `modes`, `cold_render`, `configs` and `cpu_baseline`
+(with its parity sample); --no-modes, --configs and --no-cpu-baseline trim it.
+`--dump-outputs DIR` writes the image of the last timed step, the [H, W, 3]
+per-pixel sums a caller of the timed path receives, as DIR/image.npy in the
+run's precision with the non-finite sums (the reference's NaN pixels) written
+as 0 and flagged in DIR/image_nonfinite.npy (dump_outputs); the scene, the camera and every step's seed are fixed, so
+two runs with the same arguments render the same inputs.
 
 `--gpus N` > 1 without torchrun renders on N GPUs from this one process
 through the C-ABI's multi-device context (rtw_create_devices: one rank per
@@ -74,15 +85,23 @@ def parse():
     ap.add_argument("--precision", choices=["f32", "f64"], default="f64",
                     help="f64: the parity mode, the reference's arithmetic, bit-identical to the oracle "
                          "(the headline; FP64 roofline); f32: the speed mode (hit64)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the secondary measurements on one GPU: modes, "
+                         "cold_render, configs and cpu_baseline with its parity sample (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the image of the last timed step ([H, W, 3] per-pixel sums, the run's "
+                         "precision, non-finite sums as 0) to DIR/image.npy and their flags to "
+                         "DIR/image_nonfinite.npy")
     ap.add_argument("--cpu-row-step", type=int, default=100,
                     help="cpu_baseline sample: the fixed image rows step/2, 3 step/2, ... (every step-th row, "
                          "stratified; no pilot, so every run times the same samples)")
     ap.add_argument("--configs", default="C3,C5",
-                    help="other BASELINE configs timed on one GPU after the headline (comma list of C3, "
-                         "C5; 'none' to skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: other BASELINE configs timed on one GPU after the headline (comma list of "
+                         "C3, C5; 'none' to skip)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--no-modes", action="store_true",
-                    help="skip the secondary single-GPU lines (f64 parity mode, f32 without f64 hit points)")
+                    help="--full: skip the secondary single-GPU lines (f64 parity mode, f32 without f64 hit "
+                         "points)")
     ap.add_argument("--accel", choices=["auto", "brute", "bvh"], default="auto")
     ap.add_argument("--tuning", default="", help="rtw_set_tuning overrides, e.g. bvh_kind=1,auto_chunk=4")
     ap.add_argument("--balance", type=int, default=1,
@@ -497,6 +516,37 @@ def config_line(name, precision, dev):
     return line
 
 
+NONFINITE_CODES = {1: np.nan, 2: np.inf, 3: -np.inf}
+
+
+def dump_outputs(path, image):
+    """--dump-outputs: the [H, W, 3] sums of the last timed step as two
+    all-finite arrays.  The reference's arithmetic leaves NaN sums in some
+    pixels (and the f64 kernels reproduce them bit for bit), so the image is
+    stored as `image.npy` -- the sums in their own precision with every
+    non-finite component written as 0 -- and `image_nonfinite.npy` -- float32,
+    the same shape: 0 where the component is finite, 1 NaN, 2 +inf, 3 -inf.
+    load_outputs() puts the two together again; nothing is lost but a NaN's
+    payload bits."""
+    os.makedirs(path, exist_ok=True)
+    image = np.asarray(image)
+    code = np.zeros(image.shape, np.float32)
+    code[np.isnan(image)] = 1
+    code[np.isposinf(image)] = 2
+    code[np.isneginf(image)] = 3
+    np.save(os.path.join(path, "image.npy"), np.where(code == 0, image, 0).astype(image.dtype))
+    np.save(os.path.join(path, "image_nonfinite.npy"), code)
+
+
+def load_outputs(path):
+    """The image a --dump-outputs run stored under `path`, non-finite sums restored."""
+    image = np.load(os.path.join(path, "image.npy"))
+    code = np.load(os.path.join(path, "image_nonfinite.npy"))
+    for c, v in NONFINITE_CODES.items():
+        image[code == c] = v
+    return image
+
+
 def resolve_launch(gpus, env, visible):
     """How this run spreads over GPUs: ("torchrun", N) -- one process per GPU,
     the driver's N > 1 launch (WORLD_SIZE set; --gpus must equal it),
@@ -591,6 +641,9 @@ def main():
                     "what": "one counting render + one all-reduce of the tile costs + rtw_split_deal, before "
                             "the warm-up"}
     elapsed = run_steps(step, a.steps, a.warmup, dist, sync, device=dev)
+    if a.dump_outputs and rank == 0:
+        # what the last timed step (seed steps - 1) left in `image`
+        dump_outputs(a.dump_outputs, image.cpu().numpy())
 
     # live per-launch kernel times of the timed steps (HIP events on the launch
     # stream) and the counters, of rank 0 (the in-process path: its first device)
@@ -673,7 +726,8 @@ def main():
     attach_pmc(out["roofline"], out["config"]["workload"], kname, sha,
                chunk_sum_bytes=W * H * -(-SPP // int(st.chunk)) * 3 * (4 if prec == rtw.RTW_F32 else 8) // world_size,
                kernel_ms=avg_ms)
-    if world_size == 1 and not a.no_modes:
+    full = a.full and world_size == 1
+    if full and not a.no_modes:
         # the same workload in the other arithmetic modes (single GPU, after the timed region)
         out["modes"] = {}
         if a.precision == "f32":
@@ -682,12 +736,12 @@ def main():
             out["modes"]["f32_hit64"] = mode_line(scene, cam, "f32", {}, a.steps, a.warmup, dev)
         out["modes"]["f32_plain"] = mode_line(scene, cam, "f32", {"hit64": 0}, a.steps, a.warmup, dev)
         out["cold_render"] = cold_render(scene, cam, prec, dev)
-    if world_size == 1 and a.configs != "none":
+    if full and a.configs != "none":
         out["configs"] = {}
         for name in filter(None, a.configs.split(",")):
             for p in (a.precision, "f32" if a.precision == "f64" else "f64"):
                 out["configs"][f"{name}_{p}"] = config_line(name, p, dev)
-    if world_size == 1 and not a.no_cpu_baseline:
+    if full and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(scene, a.cpu_row_step)
     print(json.dumps(out), flush=True)
     r.close()

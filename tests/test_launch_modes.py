@@ -55,6 +55,40 @@ def test_bench_gpus_2_without_gpus_exits_nonzero():
     assert '"metric"' not in p.stdout
 
 
+def test_plain_run_is_lean_and_full_is_an_option(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` asks for none of the
+    secondary measurements (they run only with --full), K is the number of
+    timed steps, and --dump-outputs names the directory of the image dump."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 3)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "some/dir"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "some/dir"
+
+
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+def test_dump_outputs_is_finite_and_restores_the_image(tmp_path, dtype):
+    """--dump-outputs stores the image as finite arrays only (non-finite sums
+    as 0 plus their flags), in the image's precision, and load_outputs gives
+    the image back exactly."""
+    import numpy as np
+
+    import bench
+    img = np.random.default_rng(5).random((5, 7, 3)).astype(dtype) * 500
+    img[0, 0] = np.nan
+    img[1, 2, 1] = np.inf
+    img[4, 6, 2] = -np.inf
+    bench.dump_outputs(str(tmp_path / "d"), img)
+    assert sorted(os.listdir(tmp_path / "d")) == ["image.npy", "image_nonfinite.npy"]
+    stored, code = np.load(tmp_path / "d" / "image.npy"), np.load(tmp_path / "d" / "image_nonfinite.npy")
+    assert stored.dtype == img.dtype and code.dtype == np.float32 and stored.shape == code.shape == img.shape
+    assert np.isfinite(stored).all() and np.isfinite(code).all()
+    assert int((code != 0).sum()) == 5 and np.array_equal(stored[code == 0], img[code == 0])
+    assert np.array_equal(bench.load_outputs(str(tmp_path / "d")), img, equal_nan=True)
+
+
 def _create(devs, prec=rtw.RTW_F64):
     arr = (C.c_int * max(len(devs), 1))(*devs)
     out = C.c_void_p(12345)

@@ -24,7 +24,7 @@ timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smo
 rc=$?; echo "smoke rc=$rc"; tail -3 "$OUT/smoke_$TAG.log"
 if fatal $rc; then exit $rc; fi
 
-timeout -k 10 600 python bench.py --steps "$STEPS" --warmup 2 > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err"
+timeout -k 10 600 python bench.py --full --steps "$STEPS" --warmup 2 > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err"
 rc=$?; echo "bench rc=$rc"; cut -c1-1500 "$OUT/bench_$TAG.json"; tail -3 "$OUT/bench_$TAG.err"
 if [ $rc -ne 0 ]; then exit $rc; fi
 
