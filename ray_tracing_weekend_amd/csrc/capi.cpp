@@ -469,7 +469,7 @@ std::vector<unsigned char> stage_scene(const rtw_scene* s, rtw::DevScene<R>* ds,
     const size_t o_lgsph = reserve(sizeof(R4) * lg.items.size());
     const size_t o_lgid = reserve(sizeof(uint32_t) * lg.items.size());
     // f64: the grid's lights rounded to f32 with |r| -- the f64 kernels' walk runs
-    // in f32 on them (render_kernel.hpp lights_pdf_grid_coop64)
+    // in f32 on them (light_pdf.hpp lights_pdf_grid_coop64)
     const size_t o_lgsph32 = reserve(std::is_same<R, double>::value ? sizeof(rtw::R4<float>) * lg.items.size() : 0);
     // the cells' records (light_grid.hpp light_grid_walk_piece_rec): 64 B per cell
     const size_t n_cells = lg.start.empty() ? 0 : lg.start.size() - 1;
@@ -1234,13 +1234,12 @@ int render_device_t(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t r
         // (bvh32) | leaf spheres | ids (padded to 8) | lights | (f32) light pairs | (f64) the lights rounded to f32
         // wide workgroups (rtw_kernels.h block_waves): the f64 kernel of sphere + plane
         // scenes with a linear light list -- 16 waves share one copy, which then also
-        // holds the f64 leaf spheres (32 B each, 32-B aligned)
+        // holds the f64 spheres twice, in leaf and in id order (32 B each, 32-B aligned)
         const bool wide = sizeof(R) == 8 && p.light_bvh == 0 && !p.sc.mat_tex &&
-                          !(p.sc.n_quads || p.sc.n_boxes || p.sc.lref || p.sc.emissive) &&
-                          rtw::block_waves(true) == rtw::kWavesWide;
+                          !(p.sc.n_quads || p.sc.n_boxes || p.sc.lref || p.sc.emissive);
         const uint32_t block_waves = rtw::block_waves(wide);
         const size_t tree_lds = rtw::traversal_lds<R>(bin_stack, p.light_bvh != 0, block_waves) +
-                                (wide ? 32 + (RTW_WIDE_SPH64 ? 2 : 1) * (size_t)p.sc.n_sph * sizeof(rtw::R4<double>) : 0) +
+                                (wide ? 32 + 2 * (size_t)p.sc.n_sph * sizeof(rtw::R4<double>) : 0) +
                                 (size_t)p.sc.n_nodes * sizeof(rtw::BvhNode<float>) +
                                 (size_t)p.sc.n_sph * sizeof(rtw::R4<float>) +
                                 (size_t)((p.sc.n_sph + 7u) & ~7u) * sizeof(uint32_t) +

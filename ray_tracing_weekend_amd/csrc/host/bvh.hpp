@@ -66,7 +66,7 @@ Bvh4Build collapse_bvh4(const BvhBuild& b);
 std::vector<uint8_t> isolated_spheres(const double* spheres, uint32_t n, const BvhBuild& b, double margin);
 
 // Uniform grid over the light spheres for the light pdf's all-hits query
-// (render_kernel.hpp light_grid_walk).  Cell c lists every light whose
+// (light_grid.hpp light_grid_walk).  Cell c lists every light whose
 // padded AABB overlaps it, in ascending light index; lights that are not
 // finite, larger than kGridBigRadius x the median radius or span more than
 // kGridBigCells cells form the "big" list every ray tests.  The grid box (lo, lo + n * cell) holds every listed light's AABB.

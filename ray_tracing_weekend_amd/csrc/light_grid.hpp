@@ -1,5 +1,5 @@
 // light_grid.hpp -- the light grid's cell walk (the light pdf's all-hits
-// query over long light lists, render_kernel.hpp lights_pdf_grid).  Host +
+// query over long light lists, light_pdf.hpp lights_pdf_grid).  Host +
 // device: tests/native/grid_walk_check.cpp runs the f64 instance on the CPU
 // against a brute-force sweep (every hit light counted exactly once), whole
 // and cut into pieces as the wave-cooperative walk cuts it.
@@ -194,7 +194,9 @@ __host__ __device__ inline void light_grid_walk_cells(const DevScene<R>& sc, V3<
 
 // light_grid_walk_cells with item(k, te, tx) for every light k listed in a
 // visited cell (two dependent loads per cell: the cell's range, then its
-// lights)
+// lights).  The kernels walk the cell records (light_grid_walk_piece_rec
+// below); this range walk is the reference tests/native/grid_walk_check.cpp
+// checks the record walk against.
 template <typename R, typename Item>
 __host__ __device__ inline void light_grid_walk_piece(const DevScene<R>& sc, V3<R> o, V3<R> d, R ix, R iy, R iz, R t0, R t1,
                                              bool head, bool tail, Item&& item, uint32_t* ncell = nullptr) {
@@ -240,34 +242,14 @@ __host__ __device__ inline void light_grid_walk_piece_rec(const DevScene<R>& sc,
         item(s3, [&]() { return sc.lg_start[c] + 3u; }, te, tx);
         for (uint32_t q = lb; q < lb + ln; ++q) item(items[q], [q]() { return q; }, te, tx);
     };
-#if RTW_GRID_PF
-    // one cell ahead: a cell's record is loaded before the previous cell's
-    // tests run, so two of a lane's record loads are in flight
-    bool have = false;
-    uint32_t pc = 0;
-    R pte = 0, ptx = 0;
-    R4<float> p0{}, p1{}, p2{}, p3{};
-    light_grid_walk_cells(sc, o, d, ix, iy, iz, t0, t1, head, tail, [&](uint32_t c, R te, R tx) {
-        const R4<float>* r = rec + (size_t)kGridRecSlots * c;
-        const R4<float> s0 = r[0], s1 = r[1], s2 = r[2], s3 = r[3];
-        if (have) tests(pc, pte, ptx, p0, p1, p2, p3);
-        have = true;
-        pc = c;
-        pte = te;
-        ptx = tx;
-        p0 = s0;
-        p1 = s1;
-        p2 = s2;
-        p3 = s3;
-    });
-    if (have) tests(pc, pte, ptx, p0, p1, p2, p3);
-#else
+    // (loading each record one cell ahead of its tests kept two loads in flight per
+    // lane but spilled 46-49 VGPRs: C5 f32 +3 %, C3 f32 +16 %,
+    // profiles/r06n_ab_grid_prefetch.jsonl)
     light_grid_walk_cells(sc, o, d, ix, iy, iz, t0, t1, head, tail, [&](uint32_t c, R te, R tx) {
         const R4<float>* r = rec + (size_t)kGridRecSlots * c;
         const R4<float> s0 = r[0], s1 = r[1], s2 = r[2], s3 = r[3];
         tests(c, te, tx, s0, s1, s2, s3);
     });
-#endif
 }
 
 }  // namespace dev

@@ -1,7 +1,7 @@
 // render_f32.hip -- speed-mode (f32) instantiation of the render kernels.
 // Built with -ffp-contract=on (FMA within a source expression) and native
 // sqrt/rcp/rsq/sin/cos.
-#include "render_kernel.hpp"
+#include "render_launch.hpp"
 
 namespace rtw {
 

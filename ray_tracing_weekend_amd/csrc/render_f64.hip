@@ -1,7 +1,7 @@
 // render_f64.hip -- parity-mode (f64) instantiation of the render kernels.
 // Built with -ffp-contract=off: every a*b+c rounds twice, in the reference's
 // operation order, so the output is bit-comparable with the CPU oracle.
-#include "render_kernel.hpp"
+#include "render_launch.hpp"
 
 namespace rtw {
 

@@ -9,7 +9,7 @@
 #endif
 #undef RTW_FASTDIV
 #define RTW_FASTDIV RTW_FASTDIV_LGRID
-#include "render_kernel.hpp"
+#include "render_launch.hpp"
 
 namespace rtw {
 

@@ -107,12 +107,8 @@ struct P<double> {
     __device__ static __forceinline__ double sqrt_(double x) { return __builtin_sqrt(x); }
     __device__ static __forceinline__ double div_(double a, double b) { return a / b; }
     __device__ static __forceinline__ double over_pi(double a) {
-#if RTW_FASTDIV >= 2
-        // (experiment) the fast quotient with a constant reciprocal of pi: the compiler folds
-        // rcp(pi) to RN(1 / pi), so the result is the IEEE one by Markstein's theorem
-        // (y = RN(1 / b), q = RN(a y) within an ulp: RN(q + (a - b q) y) = RN(a / b))
-        if (__builtin_expect(div_rng(a) <= 766u, 1)) return div_by(a, kPi, recip_nr(kPi));
-#endif
+        // (the fast quotient with a folded constant reciprocal of pi gained nothing:
+        // C2 f64 113.69 -> 113.61 ms)
         return a / kPi;
     }
     __device__ static __forceinline__ double min_(double a, double b) { return __builtin_fmin(a, b); }
@@ -509,9 +505,7 @@ __device__ __forceinline__ V3<R> sphere_random(V3<R> c, R radius, V3<R> o, Rng& 
 // the operations are those of the separate sampler, so the result is the
 // same bit for bit (f64: the oracle's rtwo_sphere_random /
 // rtwo_cosine_hemisphere).
-// kTrig32 (the f32 kernels' f64 Lambertian direction, RTW_HIT64_LAMB64): the
-// azimuth's sine and cosine by the f32 hardware instructions, the rest in R
-template <typename R, bool kTrig32 = false>
+template <typename R>
 __device__ __forceinline__ V3<R> mixture_direction(bool to_light, V3<R> n, V3<R> c, R radius, V3<R> o, Rng& g) {
     // one Onb per lane: the light direction's (Sphere::random) or the normal's
     // (CosinePdf::generate), built by the same code for both
@@ -527,14 +521,7 @@ __device__ __forceinline__ V3<R> mixture_direction(bool to_light, V3<R> n, V3<R>
     const R r1 = P<R>::u_std(g.next());
     const R r2 = P<R>::u_std(g.next());
     R s, cph;
-    if constexpr (kTrig32 && sizeof(R) == 8) {
-        float sf, cf;
-        P<float>::sincos_2pi((float)(to_light ? r2 : r1), &sf, &cf);
-        s = (R)sf;
-        cph = (R)cf;
-    } else {
-        P<R>::sincos_2pi(to_light ? r2 : r1, &s, &cph);
-    }
+    P<R>::sincos_2pi(to_light ? r2 : r1, &s, &cph);
     const R t = P<R>::sqrt_((R)1 - (to_light ? q : r2));   // light: sqrt(1 - r^2/d^2); cosine: z
     R z, sxy;
     if constexpr (sizeof(R) == 4) {

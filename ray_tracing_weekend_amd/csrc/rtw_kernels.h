@@ -7,6 +7,53 @@
 #include <stddef.h>
 #include <stdint.h>
 
+// Numeric tuning knobs (none selects a code path): the defaults are the
+// product's, tools/build_variant.py -D... overrides one for an A/B build.
+//
+// Waves per SIMD the render kernels ask for (render_kernel.hpp
+// kernel_occupancy).  f32: 5 (<= 96 VGPRs), 4 for the hit64 kernels.
+#ifndef RTW_WAVES
+#define RTW_WAVES 5
+#endif
+#ifndef RTW_WAVES_H64
+#define RTW_WAVES_H64 4
+#endif
+// f64 sphere + plane kernels (no quads / cuboids / textures): 4 waves per SIMD
+// (128 VGPRs, ~50 spilled: C2 184 -> 174 ms vs 153 VGPRs at 3 waves); the
+// other f64 kernels keep the compiler's choice.
+#ifndef RTW_WAVES_F64
+#define RTW_WAVES_F64 4
+#endif
+// f64 kernels with the light grid / BVH (C3, C5): 3 waves per SIMD -- the
+// cooperative grid walk on top of the f64 path state needs ~170 VGPRs (at 128
+// the compiler spilled the loop-carried state at every trip)
+#ifndef RTW_WAVES_F64_LBVH
+#define RTW_WAVES_F64_LBVH 3
+#endif
+// f32 (hit64) kernels with the light grid / BVH: 4 waves per SIMD (3, 168
+// VGPRs: C3 / C5 f32 +15 % time; profiles/r05_f32_list_waves_ab.jsonl)
+#ifndef RTW_WAVES_H64_LBVH
+#define RTW_WAVES_H64_LBVH 4
+#endif
+// render_kernel's issue priorities in rotation: a wave's priority changes
+// every 2^RTW_PRIO_SHIFT clock ticks (see the trip loop)
+#ifndef RTW_PRIO_SHIFT
+#define RTW_PRIO_SHIFT 12
+#endif
+// reduce_chunks_kernel, f64: chunks staged per pass (kFoldWindow)
+#ifndef RTW_FOLD_WIN64
+#define RTW_FOLD_WIN64 12
+#endif
+// the f64 cooperative grid walk (lights_pdf_grid_coop64): list indices one
+// piece keeps per pass (its LDS slot: count + ids), and that a ray's owner
+// sums per pass
+#ifndef RTW_COOP64_PIECE_IDS
+#define RTW_COOP64_PIECE_IDS 6
+#endif
+#ifndef RTW_COOP64_MAX
+#define RTW_COOP64_MAX 8
+#endif
+
 namespace rtw {
 
 constexpr uint32_t kTile = 8;          // 8 x 8 pixel tile = one wavefront of 64 lanes
@@ -16,20 +63,13 @@ constexpr uint32_t kBlock = 64 * kWavesPerBlock;
 // LDS runs 16 waves per workgroup -- the 4 waves per SIMD of one CU, so ONE
 // LDS copy of the scene per CU instead of four -- and spends the freed LDS on
 // the f64 leaf spheres, which the 4-wave layout had to read from L1 / L2 in
-// the leaf loop (a dependent global load per candidate).  0: 4 waves.
-#ifndef RTW_WIDE_F64
-#define RTW_WIDE_F64 1
-#endif
-// RTW_WIDE_SPH64: the wide kernel's LDS also holds the f64 spheres in id order
-// (the own-sphere test that starts each traversal)
-#ifndef RTW_WIDE_SPH64
-#define RTW_WIDE_SPH64 1
-#endif
+// the leaf loop (a dependent global load per candidate), and on the f64
+// spheres in id order (the own-sphere test that starts each traversal).
 constexpr uint32_t kWavesWide = 16;
 // waves per workgroup of a render kernel: `wide` = f64, tree in LDS, no
 // light BVH / grid, no quads / cuboids / textures (the Book-1 family)
 __host__ __device__ constexpr uint32_t block_waves(bool wide) {
-    return (RTW_WIDE_F64 != 0 && wide) ? kWavesWide : kWavesPerBlock;
+    return wide ? kWavesWide : kWavesPerBlock;
 }
 
 // world query of the render kernel
@@ -193,37 +233,10 @@ constexpr uint32_t kWalkStashMax = 48; // per-lane LDS words the light grid's wa
 // path state per lane in the wave's stack area (render_kernel.hpp), so the
 // host gives them at least kCoopStash + 1 entries
 constexpr uint32_t kCoopStash = 20;
-// f64 light-grid kernels: the walk parks the RNG state, the ray and (when
-// RTW_STASH64_EXTRA) the path throughput and the pending bounce's weights
-#ifndef RTW_STASH64_EXTRA
-#define RTW_STASH64_EXTRA 1
-#endif
-constexpr uint32_t kCoopStash64 = RTW_STASH64_EXTRA ? 34u : 20u;
-// the f64 cooperative grid walk (lights_pdf_grid_coop64): list indices one
-// piece keeps per pass (its LDS slot: count + ids), and that a ray's owner
-// sums per pass
-#ifndef RTW_COOP64_PIECE_IDS
-#define RTW_COOP64_PIECE_IDS 6
-#endif
-// the f64 list walk's owners merge only the pieces that hold a candidate
-// (a ballot mask per round of <= 64 pieces); 0: every piece's slot
-#ifndef RTW_COOP_HELD
-#define RTW_COOP_HELD 1
-#endif
-// the f64 list walk's pieces keep their candidates in registers (one
-// compare-exchange insert each) and write their slot once (C5 f64 1527 ->
-// 1460 ms, C3 1042 -> 1004, profiles/r06m_ab_piece_reg.jsonl); 0: insertion in LDS
-#ifndef RTW_PIECE_REG
-#define RTW_PIECE_REG 1
-#endif
-// the light grid's piece walks load each cell's record one cell ahead of its
-// tests (two loads in flight per lane); 0: load, then test
-#ifndef RTW_GRID_PF
-#define RTW_GRID_PF 0
-#endif
-#ifndef RTW_COOP64_MAX
-#define RTW_COOP64_MAX 8
-#endif
+// f64 light-grid kernels: the walk parks the RNG state, the ray, the path
+// throughput and the pending bounce's weights
+constexpr uint32_t kCoopStash64 = 34;
+// the f64 cooperative grid walk: list indices one piece keeps per pass
 constexpr uint32_t kCoop64PieceIds = RTW_COOP64_PIECE_IDS;
 // ... and the LDS words of one piece's slot per round: [count, list indices],
 // padded to 8 (16-byte reads).  The host gives the f64 light-grid kernels
@@ -232,7 +245,7 @@ constexpr uint32_t kCoop64PieceIds = RTW_COOP64_PIECE_IDS;
 constexpr uint32_t kCoop64Slot = 8;
 static_assert(kCoop64PieceIds + 1 <= kCoop64Slot, "a piece's slot holds its count and ids");
 static_assert(kCoopStash64 + kCoop64Slot <= kWalkStashMax, "the walk's LDS area fits the host's bound");
-// Subtree stealing in the while-while traversal (render_kernel.hpp
+// Subtree stealing in the while-while traversal (bvh_traverse.hpp
 // bvh_traverse_steal): per wave the result slots of its 64 rays (f32: a u64
 // key; f64: u64 t bits + u32 id) and 64 rendezvous bytes, in LDS right after
 // the traversal stacks of the workgroup's waves.

@@ -1,7 +1,7 @@
-// rtw_probes.hpp -- experiment-only hooks of the render kernel (never in the
-// product build: render_kernel.hpp includes this file only when RTW_EXP,
-// RTW_TRACE, RTW_PROF, RTW_TIMELINE or RTW_ABL is defined; otherwise every
-// RTW_PROBE_* hook is empty).
+// rtw_probes.hpp -- experiment-only hooks of the render kernel.
+// render_kernel.hpp always includes this file; in the product build (none of
+// RTW_EXP, RTW_ABL, RTW_TRACE, RTW_PROF, RTW_CLOCK, RTW_TIMELINE or
+// RTW_NANORIGIN defined) every RTW_PROBE_* hook is empty, and so is its code.
 //
 // RTW_ABL (timing ablations of the kOptHit64 parts): 1 = the
 // own-sphere re-hit test in f32, 2 = the winner's t from the f32 traversal,

@@ -118,7 +118,7 @@ int main() {
                     const double tc = -((o.x - l.x) * d.x + (o.y - l.y) * d.y + (o.z - l.z) * d.z) * ia;
                     if (tc >= te && tc < tx && hit_class(&L[4 * g.items[q]], o, d) >= 0) ++count[g.items[q]];
                 });
-                // the same walk cut into pieces (render_kernel.hpp lights_pdf_grid_coop):
+                // the same walk cut into pieces (light_pdf.hpp lights_pdf_grid_coop):
                 // k = ceil(cells / P) pieces of equal length in t
                 std::vector<int> pc(3 * n, 0);
                 {

@@ -1,5 +1,5 @@
 """The list-order merge of the f64 wave-cooperative light-grid walk
-(render_kernel.hpp lights_pdf_grid_coop64), restated in Python: a ray's hit
+(light_pdf.hpp lights_pdf_grid_coop64), restated in Python: a ray's hit
 lights are found by several pieces of its walk (and the big list), each piece
 keeps only its kPieceIds smallest list indices >= lo, the ray's owner keeps
 its kMax smallest of what it is offered, and every index up to `bound` (the

@@ -76,7 +76,7 @@ def test_full_frame_f32_tracks_f64(config, n, spp):
 def test_cooperative_grid_walk_matches_lane_walk(config, n, spp):
     """The wave-cooperative light-grid walk (grid_piece = P > 0, the default:
     every lane of the wave walks pieces of the pending rays' walks,
-    render_kernel.hpp lights_pdf_grid_coop) against one lane per ray
+    light_pdf.hpp lights_pdf_grid_coop) against one lane per ray
     (grid_piece = 0).  Both count the same lights (the pieces partition the
     walk: tests/native/grid_walk_check.cpp); only the f32 sum of a multi-piece
     ray's pdfs is associated by piece, so the frames agree to f32 rounding,

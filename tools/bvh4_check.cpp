@@ -96,7 +96,7 @@ int main(int argc, char** argv) {
                 d.child[q] = valid ? s.child[slot] : rtw::leaf_code(0, 0);
             }
         }
-    // traversal restated (render_kernel.hpp bvh4_traverse, one lane)
+    // traversal restated (bvh_traverse.hpp bvh4_traverse, one lane)
     std::uniform_real_distribution<double> D(-1, 1), O(-14, 14);
     long visits = 0, tests = 0;
     int max_sp = 0;

@@ -1,5 +1,5 @@
 // steal_sim.cpp -- lockstep simulation of the kernel's while-while BVH
-// traversal (render_kernel.hpp bvh_traverse_ww) over the ray batches of
+// traversal (bvh_traverse.hpp bvh_traverse_ww) over the ray batches of
 // tools/steal_sim.py, with and without intra-wave subtree stealing: a lane
 // with nothing left to traverse (its own ray done, or skipped) takes the
 // bottom entry of another lane's stack together with that lane's ray, and

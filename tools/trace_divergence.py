@@ -6,13 +6,20 @@ first segment whose closest hit is another object (t differs at the f32
 level from the first segment on: hit64's camera ray is f32).  Each divergence is classified by the object the ray starts on
 (the previous segment's hit) and its material, and by whether one precision
 re-hits that object (an acne re-hit: the entry of a Metal trap, DESIGN.md
-§2b) where the other does not.  Build the trace library with the reference
-rejection sampler in hit64 so both precisions draw the same words through
-Metal bounces:
+§2b) where the other does not.  The recorded analysis built the trace
+library with the reference rejection sampler in hit64, so that both
+precisions draw the same words through Metal bounces.  That variant
+(-DRTW_HIT64_REF_SPHERE=1) has since been removed from the kernel: it needs
+a checkout from before the removal (CHANGELOG.md), where
 
     TRACE_VAR=build/variants/traceref TRACE_FLAGS=-DRTW_HIT64_REF_SPHERE=1 \\
         python tools/trace_paths.py build
-    TRACE_VAR=build/variants/traceref python tools/trace_paths.py run --out X.npz --pixels ...
+
+builds it.  The current kernel's two precisions draw different words at a
+Metal bounce (direct sampler vs rejection loop), so paths part there at the latest:
+
+    python tools/trace_paths.py build
+    python tools/trace_paths.py run --out X.npz --pixels ...
     python tools/trace_divergence.py X.npz
 """
 import collections

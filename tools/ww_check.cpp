@@ -1,5 +1,5 @@
 // ww_check.cpp -- host-only lockstep simulation of the binary while-while
-// traversal in render_kernel.hpp (bvh_traverse_ww): 64 lanes execute the
+// traversal in bvh_traverse.hpp (bvh_traverse_ww): 64 lanes execute the
 // same iteration with the kernel's wave-uniform loop conditions; every lane's
 // closest sphere must equal brute force, every wave must terminate, and the
 // stack must stay within `depth` entries (the kernel sizes it so).
