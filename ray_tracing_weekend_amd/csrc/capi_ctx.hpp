@@ -1,0 +1,210 @@
+// capi_ctx.hpp -- private to the C-ABI units (capi.cpp, capi_render.cpp,
+// capi_multi.cpp): the context behind include/rtw.h's rtw_ctx and the helpers
+// they share.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>   // types only: the functions are resolved at run time (capi_multi.cpp rccl_api)
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/rtw.h"
+#include "host/render_plan.hpp"
+#include "host/stage_scene.hpp"
+#include "host/tiles.hpp"
+#include "rtw_kernels.h"
+
+// What a set of tile costs was counted for: the task order of the renders of
+// the same key follows them.
+struct LptKey {
+    rtw_camera cam;
+    uint64_t scene_serial;
+    uint32_t rank, nranks, prec;      // prec: sizeof of the precision
+    uint64_t split;                   // SplitState::id (0 = the round robin)
+    bool operator==(const LptKey& o) const {
+        return scene_serial == o.scene_serial && rank == o.rank && nranks == o.nranks && prec == o.prec &&
+               split == o.split && memcmp(&cam, &o.cam, sizeof cam) == 0;
+    }
+};
+
+// longest-tiles-first task list (pilot render, see capi_render.cpp lpt_pilot / render_plan.hpp build_task_list)
+struct LptCache {
+    void* d_cost = nullptr;           // pilot: [tile cost | chunk sums | tiles]
+    size_t cost_cap = 0;
+    bool valid = false;               // h_cost is the pilot of `key`
+    bool pending = false;             // ... still on the device: counted by the render before (ev)
+    hipEvent_t ev = nullptr;
+    LptKey key{};
+    std::vector<uint32_t> h_cost;
+    void* d_tasks = nullptr;          // the task list of (h_cost, tab_*)
+    size_t tasks_cap = 0;
+    bool tab_valid = false;
+    uint32_t tab_chunks = 0, tab_group = 0;
+    uint64_t tab_target = 0;
+    std::vector<uint32_t> h_tasks;
+    // the context holds (or has pending) tile costs of this key
+    bool has(const LptKey& k) const { return (valid || pending) && key == k; }
+};
+
+// Rank split (ABI 10): renders of a W x H image over n ranks give tile T to
+// rank rank[T] (rtw_set_split; empty: T mod n, the round robin).  Each rank
+// keeps the round robin's tile COUNT, so the packed buffers and the gather are
+// unchanged.  cost: the tile costs the split was dealt by -- they order the
+// next renders' tasks (no counting render after a deal).  automatic: dealt by
+// rtw_render_image_device (tuning "balance") for cam / scene, re-dealt when
+// they change.
+struct SplitState {
+    uint32_t W = 0, H = 0, n = 0;
+    uint64_t serial = 0;              // ++ per split set: the split's id in the task-order key
+    bool automatic = false;
+    rtw_camera cam{};
+    uint64_t scene = 0;
+    std::vector<uint32_t> rank, cost;
+    // the device copies of the split: this rank's local tile -> global tile (render
+    // kernel) and global tile -> lt * n + rank (assembly), for split id *_key
+    std::vector<uint32_t> h_tile_map;
+    void* d_tile_map = nullptr;
+    size_t tile_map_cap = 0;
+    uint64_t tile_map_key = 0;
+    uint32_t tile_map_rank = 0;
+    void* d_tile_slot = nullptr;
+    size_t tile_slot_cap = 0;
+    uint64_t tile_slot_key = 0;
+    // a split is set for renders of this image size and rank count
+    bool active(uint32_t w, uint32_t h, uint32_t nranks) const {
+        return !rank.empty() && W == w && H == h && n == nranks;
+    }
+    // the id of the split renders of (w, h, nranks) follow: 0 = the round robin
+    uint64_t id(uint32_t w, uint32_t h, uint32_t nranks) const { return active(w, h, nranks) ? serial : 0; }
+    // the global tiles of rank r, in the order they are packed
+    void local_tiles(uint32_t w, uint32_t h, uint32_t r, uint32_t nranks, std::vector<uint32_t>& out) const {
+        rtw::local_tiles(active(w, h, nranks) ? &rank : nullptr, w, h, r, nranks, out);
+    }
+};
+
+struct rtw_ctx {
+    int device = 0;
+    int precision = RTW_F32;
+    rtw::RenderKnobs knobs;
+    size_t dev_total = 0;         // the device's memory (hipMemGetInfo), 0 until asked
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // ring of per-render event triples: [start, after render kernel, after reduce]
+    static constexpr int kRing = 64;
+    hipEvent_t ring[kRing][3] = {};
+    uint64_t n_renders = 0;
+    // device scene (one allocation holding every array)
+    void* d_scene = nullptr;
+    size_t scene_bytes = 0;           // allocation
+    size_t scene_used = 0;            // the current scene's bytes
+    rtw::SceneScale scale;            // of the staged scene (knob robust = 2, the lpt heuristic)
+    rtw::DevScene<float> sc32{};
+    rtw::DevScene<double> sc64{};
+    bool has_scene = false;
+    uint64_t scene_serial = 0;        // ++ per rtw_upload_scene
+    // work buffers
+    void* d_partial = nullptr;
+    size_t partial_cap = 0;
+    void* d_out = nullptr;        // rtw_render: the packed tiles, then the image
+    size_t out_cap = 0;
+    void* d_img = nullptr;
+    size_t img_cap = 0;
+    static constexpr int kCounters = 9;   // rtw_kernels.h KParams::counters
+    unsigned long long* d_counters = nullptr;
+    std::vector<unsigned char> h_out;
+    LptCache lpt;
+    SplitState split;
+    rtw_stats last{};
+    int last_variant = 0;             // render kernel of the last render: launch_render_impl's code
+    uint32_t last_n_sph = 0;
+    uint32_t last_light_bvh = 0;      // KParams::light_bvh of the last render (0: the linear light loop)
+    uint32_t last_n_list = 0;         // ... and its light-list length
+    std::string err;
+    // multi-device context (rtw_create_devices): this context is rank 0 on the
+    // first device; peers[k - 1] is the context of rank k on device k of the
+    // list, mirroring every knob and the scene.  One RCCL communicator per rank
+    // (a single-process clique) for the framebuffer gather to rank 0.
+    bool multi = false;
+    std::vector<rtw_ctx*> peers;
+    std::vector<ncclComm_t> comms;
+    void* d_gather = nullptr;         // rank 0's device: the n ranks' packed tiles (gather target)
+    size_t gather_cap = 0;
+    // virtual ranks (rtw_create_virtual, a test mode): every rank on one device,
+    // the gather done by device copies on rank 0's stream after peer_ev[k - 1]
+    bool virt = false;
+    std::vector<hipEvent_t> peer_ev;
+    // the last multi-device gather + assembly, on rank 0's stream of that call:
+    // the next call's renders (every rank) wait for it before they overwrite
+    // d_gather or a peer's packed tiles
+    hipEvent_t gather_ev = nullptr;
+    bool gather_pending = false;
+    // ranks whose counters the last render filled (rtw_get_stats): n after
+    // rtw_render / rtw_render_image_device, 1 after rtw_render_device
+    uint32_t stats_ranks = 1;
+};
+
+static inline int fail(rtw_ctx* c, int code, const std::string& msg) {
+    if (c) c->err = msg;
+    return code;
+}
+static inline int hip_fail(rtw_ctx* c, hipError_t e, const char* what) {
+    return fail(c, RTW_E_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+}
+#define HIP_TRY(ctx, expr)                                   \
+    do {                                                     \
+        hipError_t e_ = (expr);                              \
+        if (e_ != hipSuccess) return hip_fail(ctx, e_, #expr); \
+    } while (0)
+
+static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// grow a device buffer to at least `bytes` (its contents are not kept)
+static inline int ensure(rtw_ctx* c, void** buf, size_t* cap, size_t bytes) {
+    if (*cap >= bytes) return RTW_OK;
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    HIP_TRY(c, hipMalloc(buf, bytes));
+    *cap = bytes;
+    return RTW_OK;
+}
+
+// the caller's stream argument: NULL = the context's own stream,
+// RTW_STREAM_NULL = the device's null (legacy default) stream, else a hipStream_t
+static inline hipStream_t resolve_stream(const rtw_ctx* c, void* stream) {
+    if (!stream) return c->stream;
+    if (stream == RTW_STREAM_NULL) return nullptr;
+    return reinterpret_cast<hipStream_t>(stream);
+}
+
+// the key of tile costs counted by a render of (cam, rank, nranks) on this context
+static inline LptKey lpt_key(const rtw_ctx* c, const rtw_camera* cam, uint32_t rank, uint32_t nranks) {
+    return LptKey{*cam, c->scene_serial, rank, nranks, c->precision == RTW_F32 ? 4u : 8u,
+                  c->split.id(cam->image_width, cam->image_height, nranks)};
+}
+
+// multi-device: every rank alike -- f(peer context) on each peer; the first
+// failure is reported on c
+template <typename F>
+int on_peers(rtw_ctx* c, F&& f) {
+    for (rtw_ctx* pk : c->peers) {
+        const int rc = f(pk);
+        if (rc) return fail(c, rc, pk->err);
+    }
+    return RTW_OK;
+}
+
+// capi.cpp: the split (and its costs) on one rank context; tile_rank NULL: the round robin
+int apply_split(rtw_ctx* c, uint32_t W, uint32_t H, uint32_t nranks, const uint32_t* tile_rank,
+                const uint32_t* tile_cost, bool automatic, const rtw_camera* cam);
+// capi.cpp: the stats of the last render of one rank context (rtw_get_stats sums them)
+int get_stats_one(rtw_ctx* c, rtw_stats* out);
+// capi_render.cpp: the tile costs the context counted for (cam, rank, nranks) under
+// its split, scattered into cost[global tile]; waits for a pending counting render
+int tile_costs_of(rtw_ctx* c, const rtw_camera* cam, uint32_t rank, uint32_t nranks, uint32_t* cost);
+// capi_multi.cpp: rtw_destroy's part for the ranks of a multi-device context
+void destroy_ranks(rtw_ctx* c);

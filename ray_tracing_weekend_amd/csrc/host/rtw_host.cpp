@@ -546,3 +546,209 @@ std::tuple<HittableList, HittableList, CameraBuilder> simple_transform(uint64_t 
 }  // namespace scenes
 
 }  // namespace rtw
+
+// ---------------------------------------------------------------- C-ABI
+// The entry points of include/rtw.h that are pure host code: CameraBuilder::
+// build, the scene generators, the Perlin tables and the output encoding.
+extern "C" {
+
+void rtw_camera_builder_default(rtw_camera_builder* b) {
+    // CameraBuilder::new(), camera.rs:45-60
+    memset(b, 0, sizeof(*b));
+    b->samples_per_pixel = 10;
+    b->max_depth = 10;
+    b->vfov = 90.0;
+    b->lookat[2] = -1.0;
+    b->vup[1] = 1.0;
+    b->defocus_angle = 0.0;
+    b->focus_dist = 10.0;
+}
+
+static uint32_t round_u32(double x) {
+    // f64::round (half away from zero) then `as u32` (saturating, NaN -> 0)
+    double r = round(x);
+    if (!(r > 0.0)) return 0;
+    if (r >= 4294967295.0) return 4294967295u;
+    return (uint32_t)r;
+}
+
+int rtw_camera_build(const rtw_camera_builder* b, rtw_camera* out) {
+    // CameraBuilder::build, camera.rs:114-218
+    if (!b || !out) return RTW_E_INVALID;
+    struct V { double x, y, z; };
+    auto sub = [](V a, V c) { return V{a.x - c.x, a.y - c.y, a.z - c.z}; };
+    auto add = [](V a, V c) { return V{a.x + c.x, a.y + c.y, a.z + c.z}; };
+    auto mul = [](V a, double s) { return V{a.x * s, a.y * s, a.z * s}; };
+    auto dv = [](V a, double s) { return V{a.x / s, a.y / s, a.z / s}; };
+    auto dot = [](V a, V c) { return a.x * c.x + a.y * c.y + a.z * c.z; };
+    auto cross = [](V a, V c) {
+        return V{a.y * c.z - a.z * c.y, a.z * c.x - a.x * c.z, a.x * c.y - a.y * c.x};
+    };
+    auto norm = [&](V a) { return dv(a, sqrt(dot(a, a))); };
+    auto ld = [](const double* p) { return V{p[0], p[1], p[2]}; };
+    auto st = [](double* p, V v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; };
+
+    const bool ha = b->has_aspect_ratio, hh = b->has_image_height, hw = b->has_image_width;
+    double aspect;
+    uint32_t H, W;
+    if (!ha && !hh && !hw) { aspect = 1.0; H = 100; W = 100; }
+    else if (!ha && !hh && hw) { aspect = 1.0; H = b->image_width; W = b->image_width; }
+    else if (!ha && hh && !hw) { aspect = 1.0; H = b->image_height; W = b->image_height; }
+    else if (ha && !hh && !hw) { aspect = b->aspect_ratio; H = round_u32(100.0 / b->aspect_ratio); W = 100; }
+    else if (!ha && hh && hw) { aspect = (double)b->image_width / (double)b->image_height; H = b->image_height; W = b->image_width; }
+    else if (ha && !hh && hw) { aspect = b->aspect_ratio; H = round_u32((double)b->image_width / b->aspect_ratio); W = b->image_width; }
+    else if (ha && hh && !hw) { aspect = b->aspect_ratio; H = b->image_height; W = round_u32((double)b->image_height * b->aspect_ratio); }
+    else { aspect = b->aspect_ratio; H = b->image_height; W = b->image_width; }
+
+    const double kPi = 3.14159265358979323846;
+    V center = ld(b->lookfrom);
+    double theta = b->vfov * (kPi / 180.0);   // f64::to_radians
+    double h = tan(theta / 2.0);
+    double vh = 2.0 * h * b->focus_dist;
+    double vw = vh * aspect;
+    V w = sub(ld(b->lookfrom), ld(b->lookat));
+    V c0 = cross(ld(b->vup), w);
+    if (fabs(c0.x) < 1e-8 && fabs(c0.y) < 1e-8 && fabs(c0.z) < 1e-8) w = add(w, V{0.1, 0.0, 0.0});
+    w = norm(w);
+    V u = norm(cross(ld(b->vup), w));
+    V v = cross(w, u);
+    V vu = mul(u, vw), vv = mul(v, vh);
+    V du = dv(vu, (double)W), dvv = dv(vv, (double)H);
+    V ul = sub(sub(sub(center, mul(w, b->focus_dist)), dv(vu, 2.0)), dv(vv, 2.0));
+    V p00 = add(ul, dv(add(du, dvv), 2.0));
+    double rad = tan(b->defocus_angle / 2.0) * b->focus_dist;
+    memset(out, 0, sizeof(*out));
+    out->image_width = W;
+    out->image_height = H;
+    out->samples_per_pixel = b->samples_per_pixel;
+    out->max_depth = b->max_depth;
+    memcpy(out->background, b->background, sizeof(out->background));
+    out->defocus_angle = b->defocus_angle;
+    st(out->center, center);
+    st(out->pixel00_loc, p00);
+    st(out->pixel_delta_u, du);
+    st(out->pixel_delta_v, dvv);
+    st(out->defocus_disk_u, mul(u, rad));
+    st(out->defocus_disk_v, mul(v, rad));
+    return RTW_OK;
+}
+
+// ------------------------------------------------------------ scenes::simple
+struct rtw_world {
+    rtw::FlatScene flat;
+    rtw_scene view;
+    rtw_camera_builder cam;
+};
+
+rtw_world* rtw_scene_simple(uint64_t seed, int grid_n) {
+    if (grid_n < 0) return nullptr;
+    try {
+        auto t = rtw::scenes::simple(seed, grid_n);
+        rtw_world* w = new rtw_world();
+        w->flat = rtw::flatten(std::get<0>(t), std::get<1>(t));
+        w->view = w->flat.view();
+        w->cam = std::get<2>(t).raw();
+        return w;
+    } catch (...) {
+        return nullptr;
+    }
+}
+const rtw_scene* rtw_world_scene(const rtw_world* w) { return w ? &w->view : nullptr; }
+void rtw_world_camera_builder(const rtw_world* w, rtw_camera_builder* out) {
+    if (w && out) *out = w->cam;
+}
+void rtw_world_free(rtw_world* w) { delete w; }
+
+rtw_world* rtw_scene_named(const char* name, uint64_t seed) {
+    if (!name) return nullptr;
+    const std::string n = name;
+    if (n == "simple") return rtw_scene_simple(seed, 11);
+    try {
+        std::tuple<rtw::HittableList, rtw::HittableList, rtw::CameraBuilder> t;
+        if (n == "cornell_box") t = rtw::scenes::cornell_box();
+        else if (n == "debug") t = rtw::scenes::debugging_scene(seed);
+        else if (n == "checkered_spheres") t = rtw::scenes::checkered_spheres();
+        else if (n == "perlin_spheres") t = rtw::scenes::perlin_spheres(seed);
+        else if (n == "plane") t = rtw::scenes::plane();
+        else if (n == "simple_light") t = rtw::scenes::simple_light(seed);
+        else if (n == "simple_transform") t = rtw::scenes::simple_transform(seed);
+        else return nullptr;
+        rtw_world* w = new rtw_world();
+        w->flat = rtw::flatten(std::get<0>(t), std::get<1>(t));
+        w->view = w->flat.view();
+        w->cam = std::get<2>(t).raw();
+        return w;
+    } catch (...) {
+    }
+    return nullptr;
+}
+
+int rtw_perlin_generate(uint64_t seed, double* rand_vec, uint32_t* perm) {
+    if (!rand_vec || !perm) return RTW_E_INVALID;
+    auto p = rtw::Perlin::generate(seed);
+    memcpy(rand_vec, p->rand_vec.data(), sizeof(double) * 768);
+    memcpy(perm, p->perm.data(), sizeof(uint32_t) * 768);
+    return RTW_OK;
+}
+
+// ------------------------------------------------------------ output encoding
+static uint8_t to_u8(double x) {
+    // (256. * x.clamp(0., 1.)) as u8 -- saturating cast, NaN -> 0 (colour.rs:32-34)
+    double c = x != x ? x : (x < 0.0 ? 0.0 : (x > 1.0 ? 1.0 : x));
+    double v = 256.0 * c;
+    if (!(v > 0.0)) return 0;
+    if (v >= 255.0) return 255;
+    return (uint8_t)v;
+}
+
+}  // extern "C"
+
+namespace {
+// write_colour, colour.rs:14-36: scale = (spp as f64).recip(); sqrt(c * scale),
+// on the f64 value of each sum (an f32 sum is widened exactly first); rows in
+// reverse, main.rs:97-104
+template <typename S>
+int encode_rgb8(const S* sums, uint32_t W, uint32_t H, uint32_t spp, uint8_t* out) {
+    if ((!sums || !out) && W && H) return RTW_E_INVALID;
+    const double scale = 1.0 / (double)(int32_t)spp;
+    for (uint32_t r = 0; r < H; ++r) {
+        const uint32_t j = H - 1 - r;
+        for (uint32_t i = 0; i < W; ++i)
+            for (int k = 0; k < 3; ++k)
+                out[((size_t)r * W + i) * 3 + k] = to_u8(sqrt((double)sums[((size_t)j * W + i) * 3 + k] * scale));
+    }
+    return RTW_OK;
+}
+
+template <typename S>
+int write_ppm(const char* path, const S* sums, uint32_t W, uint32_t H, uint32_t spp) {
+    if (!path) return RTW_E_INVALID;
+    std::vector<uint8_t> rgb((size_t)W * H * 3);
+    int rc = encode_rgb8(sums, W, H, spp, rgb.data());
+    if (rc) return rc;
+    FILE* f = fopen(path, "wb");
+    if (!f) return RTW_E_INVALID;
+    int n = fprintf(f, "P3\n%u %u\n255\n", W, H);
+    for (size_t p = 0; p < (size_t)W * H; ++p)
+        n += fprintf(f, "%u %u %u\n", rgb[3 * p], rgb[3 * p + 1], rgb[3 * p + 2]);
+    fclose(f);
+    return n;
+}
+}  // namespace
+
+extern "C" {
+
+int rtw_encode_rgb8(const double* sums, uint32_t W, uint32_t H, uint32_t spp, uint8_t* out) {
+    return encode_rgb8(sums, W, H, spp, out);
+}
+int rtw_encode_rgb8_f32(const float* sums, uint32_t W, uint32_t H, uint32_t spp, uint8_t* out) {
+    return encode_rgb8(sums, W, H, spp, out);
+}
+int rtw_write_ppm(const char* path, const double* sums, uint32_t W, uint32_t H, uint32_t spp) {
+    return write_ppm(path, sums, W, H, spp);
+}
+int rtw_write_ppm_f32(const char* path, const float* sums, uint32_t W, uint32_t H, uint32_t spp) {
+    return write_ppm(path, sums, W, H, spp);
+}
+
+}  // extern "C"

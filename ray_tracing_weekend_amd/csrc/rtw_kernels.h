@@ -1,6 +1,6 @@
 // rtw_kernels.h -- host-visible description of the device scene layout and the
 // launch entry points of the gfx950 render kernels (render_f32.hip /
-// render_f64.hip).  Included by the C-ABI (capi.cpp) and by the kernels.
+// render_f64.hip).  Included by the C-ABI (capi_ctx.hpp), host/ and the kernels.
 #pragma once
 
 #include <hip/hip_runtime.h>

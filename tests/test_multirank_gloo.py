@@ -75,7 +75,7 @@ def _worker(rank, world, port, h, w, q):
 
 
 def _worker_image_device(rank, world, port, h, w, q):
-    """The orchestration of rtw_render_image_device (capi.cpp) on a
+    """The orchestration of rtw_render_image_device (capi_multi.cpp) on a
     multi-device context, one gloo rank per device: every rank renders its
     tiles into an equal-size buffer of rank 0's tile count -- rank 0 in place,
     into slot 0 of the gather target (ncclGather's in-place form,

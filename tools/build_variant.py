@@ -12,6 +12,8 @@ import os
 import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
+from host_objs import host_objs
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CS = os.path.join(ROOT, "ray_tracing_weekend_amd", "csrc")
 OBJ = os.path.join(ROOT, "ray_tracing_weekend_amd", "build")
@@ -42,7 +44,7 @@ def main():
         list(ex.map(compile_one, precs))
     objs = [f"{var}/render_{p}.o" if p in precs else f"{OBJ}/render_{p}.o" for p in ("f32", "f64", "f64_lgrid")]
     subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", f"{var}/librtw.so",
-                    *objs, f"{OBJ}/capi.o", f"{OBJ}/rtw_host.o", f"{OBJ}/bvh.o", "-ldl"], check=True)
+                    *objs, *host_objs(), "-ldl"], check=True)
     print("built", f"{var}/librtw.so")
 
 

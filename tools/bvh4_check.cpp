@@ -26,7 +26,7 @@ static int fails = 0;
         }                              \
     } while (0)
 
-struct Node4 {   // octant copy, as staged by capi.cpp
+struct Node4 {   // octant copy, as staged by host/stage_scene.cpp
     float nx[4], ny[4], nz[4], fx[4], fy[4], fz[4];
     int32_t child[4];
 };
@@ -74,7 +74,7 @@ int main(int argc, char** argv) {
     }
     printf("average children per node %.2f\n", fill / std::max<size_t>(1, b4.nodes.size()));
     for (uint32_t k = 0; k < n; ++k) CHECK(seen[k] == 1, "sphere %u seen %d times", k, seen[k]);
-    // stage the octant copies exactly like capi.cpp
+    // stage the octant copies exactly like host/stage_scene.cpp
     const size_t n4 = b4.nodes.size();
     std::vector<Node4> nodes(8 * n4);
     for (int oct = 0; oct < 8; ++oct)

@@ -15,6 +15,8 @@ import os
 import subprocess
 import sys
 
+from host_objs import host_objs
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VAR = os.path.join(ROOT, "build", "variants", "clock")
 PARTS = {0: "item pool + sample start", 1: "planes", 2: "closest hit", 3: "hit record", 4: "Lambertian",
@@ -39,8 +41,7 @@ def build():
     # probes -- their C3 / C5 f64 clock profiles need the probes in that unit, whose
     # readers would clash with render_f64.hip's)
     subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", f"{VAR}/librtw.so",
-                    f"{VAR}/render_f32.o", f"{VAR}/render_f64.o", f"{b}/render_f64_lgrid.o", f"{b}/capi.o",
-                    f"{b}/rtw_host.o", f"{b}/bvh.o",
+                    f"{VAR}/render_f32.o", f"{VAR}/render_f64.o", f"{b}/render_f64_lgrid.o", *host_objs(),
                     "-ldl"], check=True)
     print("built", f"{VAR}/librtw.so")
 

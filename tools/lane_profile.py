@@ -13,6 +13,8 @@ import os
 import subprocess
 import sys
 
+from host_objs import host_objs
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VAR = os.path.join(ROOT, "build", "variants", "prof")
 NAMES = {1: "bvh inner step", 2: "leaf tests", 3: "segment loop (wave)", 4: "segment (active lanes)",
@@ -33,7 +35,7 @@ def build():
                     f"-I{cs}", f"-I{ROOT}/include", "-ffp-contract=off", "-DRTW_PROF=f64", "-c", f"{cs}/render_f64.hip",
                     "-o", f"{VAR}/render_f64.o"], check=True)
     subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", f"{VAR}/librtw.so",
-                    f"{VAR}/render_f32.o", f"{VAR}/render_f64.o", f"{b}/render_f64_lgrid.o", f"{b}/capi.o", f"{b}/rtw_host.o", f"{b}/bvh.o",
+                    f"{VAR}/render_f32.o", f"{VAR}/render_f64.o", f"{b}/render_f64_lgrid.o", *host_objs(),
                     "-ldl"], check=True)
     print("built", f"{VAR}/librtw.so")
 

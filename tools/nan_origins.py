@@ -17,6 +17,8 @@ import os
 import subprocess
 import sys
 
+from host_objs import host_objs, layout_units
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VAR = os.environ.get("NAN_VAR", os.path.join(ROOT, "build", "variants", "nan"))
 EXTRA = os.environ.get("NAN_FLAGS", "").split()   # extra -D flags of an experiment build
@@ -32,11 +34,17 @@ def build():
                              f"{VAR}/render_f32.o"], check=True)
     subprocess.run(common + ["-ffp-contract=off", "-DRTW_NANORIGIN=f64", "-c", f"{cs}/render_f64.hip", "-o",
                              f"{VAR}/render_f64.o"], check=True)
-    subprocess.run(common + ["-ffp-contract=off", "-c", f"{cs}/capi.cpp", "-o", f"{VAR}/capi.o"], check=True)
+    # the host units that see rtw_kernels.h's layouts are recompiled with the same
+    # flags; the other host objects come from the in-tree build
+    own = {}
+    for src in layout_units():
+        name = os.path.splitext(os.path.basename(src))[0] + ".o"
+        own[name] = f"{VAR}/{name}"
+        subprocess.run(common + ["-ffp-contract=off", "-c", src, "-o", own[name]], check=True)
+    host = [own.get(os.path.basename(o), o) for o in host_objs()]
     subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", f"{VAR}/librtw.so",
-                    f"{VAR}/render_f32.o", f"{VAR}/render_f64.o", f"{b}/render_f64_lgrid.o", f"{VAR}/capi.o", f"{b}/rtw_host.o", f"{b}/bvh.o",
-                    "-ldl"], check=True)
-    for f in ("render_f32.o", "render_f64.o", "capi.o"):
+                    f"{VAR}/render_f32.o", f"{VAR}/render_f64.o", f"{b}/render_f64_lgrid.o", *host, "-ldl"], check=True)
+    for f in ("render_f32.o", "render_f64.o", *own):
         os.remove(os.path.join(VAR, f))
     print("built", f"{VAR}/librtw.so")
 

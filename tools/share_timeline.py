@@ -15,6 +15,8 @@ import os
 import subprocess
 import sys
 
+from host_objs import host_objs
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VAR = os.path.join(ROOT, "build", "variants", "timeline")
 
@@ -31,8 +33,7 @@ def build(precision):
                    check=True)
     other = "f32" if precision == "f64" else "f64"
     subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", f"{VAR}/librtw.so",
-                    f"{VAR}/render_{precision}.o", f"{b}/render_{other}.o", f"{b}/capi.o", f"{b}/rtw_host.o",
-                    f"{b}/bvh.o"], check=True)
+                    f"{VAR}/render_{precision}.o", f"{b}/render_{other}.o", *host_objs()], check=True)
     print("built", f"{VAR}/librtw.so")
 
 
