@@ -277,7 +277,14 @@ int rtw_set_accel(rtw_ctx *ctx, int accel);
  * "bvh_kind" (3 = binary while-while on the tree staged in LDS, the
  * default, 1 = binary while-while from L1/L2, 2 = 4-wide octant BVH, 0 =
  * binary single loop), "bvh_lds_max" (LDS bytes per workgroup bvh_kind 3 may
- * use; 0 = by precision: 36 KiB f32, 52 KiB f64), "bvh_ww" (legacy: 1 -> bvh_kind 1, 0 -> 0), "auto_accel" */
+ * use; 0 = by precision: 36 KiB f32, 52 KiB f64), "bvh_ww" (legacy: 1 -> bvh_kind 1, 0 -> 0), "auto_accel",
+ * "window" (sample windows, the one key that takes a negative value: 0 = off, the
+ * default; N > 0 = every render of more than N samples per pixel runs N samples at a
+ * time -- N rounded up to a multiple of an explicit chunk -- onto an f64 accumulator of
+ * the context, so the chunk sums hold one window instead of the whole render; -1 = the
+ * largest window whose chunk sums fit "partial_max", the auto chunk then stays 1 at any
+ * spp.  Same image as the one-shot render at the same chunk, bit for bit; stats cover the
+ * whole render; rtw_get_timings then lists the windows) */
 int rtw_set_tuning(rtw_ctx *ctx, const char *key, int64_t value);
 
 /* ---- CameraBuilder::build (camera.rs:114-218) ------------------------- */
@@ -326,6 +333,33 @@ int rtw_render_image_device(rtw_ctx *ctx, const rtw_camera *cam, uint64_t seed, 
 int rtw_render_device(rtw_ctx *ctx, const rtw_camera *cam, uint64_t seed,
                       uint32_t rank, uint32_t nranks, void *d_out, size_t out_bytes,
                       void *stream);
+
+/* ---- sample windows: progressive and resumable renders -----------------
+ * Every (pixel, sample) has its own RNG stream, so a render can be taken a
+ * window of samples at a time and its running per-pixel sums continued later:
+ * windows [0, a), [a, b), ... folded one after another give the one-shot
+ * render of b samples at the same chunk bit for bit, in both precisions (the
+ * running sums are f64 whatever the context's precision: the f32 one-shot
+ * fold also accumulates in f64 and rounds once). */
+/* Samples [first_sample, first_sample + n_samples) of this rank's tiles, folded
+ * in sample order onto d_accum: tiles_for_rank * 64 * 3 doubles (always f64),
+ * packed like rtw_render_device's d_out, the sums of samples [0, first_sample)
+ * on entry (ignored when first_sample == 0) and of [0, first_sample + n_samples)
+ * afterwards.  cam->samples_per_pixel is not read.  Asynchronous on `stream`.
+ * n_samples == 0 does nothing.  RTW_E_INVALID when first_sample + n_samples
+ * overflows, first_sample is not a multiple of the chunk (rtw_set_chunk; the
+ * auto chunk is 1), d_accum is NULL or accum_bytes too small; RTW_E_UNSUPPORTED
+ * on a multi-device context (tuning "window" serves those).  Stats are the
+ * window's. */
+int rtw_render_window_device(rtw_ctx *ctx, const rtw_camera *cam, uint64_t seed,
+                             uint32_t rank, uint32_t nranks,
+                             uint32_t first_sample, uint32_t n_samples,
+                             double *d_accum, size_t accum_bytes, void *stream);
+/* Host form, one-device contexts: sums is H*W*3 doubles (j = 0 bottom row),
+ * read when first_sample > 0, written with the continued sums. Synchronous. */
+int rtw_render_window(rtw_ctx *ctx, const rtw_camera *cam, uint64_t seed,
+                      uint32_t first_sample, uint32_t n_samples,
+                      double *sums, rtw_stats *stats);
 uint32_t rtw_tile_size(void);                        /* tile edge in pixels (8) */
 uint32_t rtw_tiles_for_rank(uint32_t image_width, uint32_t image_height, uint32_t rank,
                             uint32_t nranks);

@@ -485,6 +485,25 @@ class Camera:
 
     render_debug = render                     # camera.rs:299-312 (no sequential mode on a GPU)
 
+    def render_progressive(self, world, lights, window: int, *, seed: int = 0x5EED0001,
+                           precision: int = RTW_F64, device: int = 0):
+        """The render `window` samples at a time: a generator of (samples_done,
+        sums) after each window, sums the float64 [H, W, 3] running sums (the
+        same array each time: copy it to keep a stage).  The last yield is
+        render()'s image bit for bit (at one sample per item, the default).  A
+        stage saved with np.savez continues later with
+        Renderer.render_window(cam, seed, samples_done, n, sums)."""
+        if window < 1:
+            raise RenderError(_capi.RTW_E_INVALID, "render_progressive: window must be >= 1")
+        spp = self.raw.samples_per_pixel
+        with Renderer(device=device, precision=precision) as r:
+            r.set_scene(flatten(world, lights))
+            sums = None
+            for first in range(0, spp, window):
+                n = min(window, spp - first)
+                sums = r.render_window(self, seed, first, n, sums)
+                yield first + n, sums
+
 
 class Renderer:
     """An rtw_ctx: a device (or, with `devices`, one rank per listed GPU:
@@ -581,6 +600,37 @@ class Renderer:
                                            nranks, C.c_void_p(out_ptr) if out_ptr else None, out_bytes,
                                            C.c_void_p(stream) if stream else None),
                     "rtw_render_device")
+
+    def render_window(self, cam: Camera, seed: int, first: int, n: int, sums=None) -> np.ndarray:
+        """Samples [first, first + n) of every pixel, continuing the running
+        sums `sums` (float64 [H, W, 3] of samples [0, first); not needed when
+        first == 0) in place (rtw_render_window).  Windows folded one after
+        another are the one-shot render of as many samples, bit for bit.
+        Returns the sums; cam.samples_per_pixel is not read."""
+        H, W = cam.raw.image_height, cam.raw.image_width
+        if sums is None:
+            if first:
+                raise RenderError(_capi.RTW_E_INVALID, "render_window: first > 0 continues `sums`")
+            sums = np.zeros((H, W, 3), np.float64)
+        if sums.dtype != np.float64 or sums.shape != (H, W, 3) or not sums.flags.c_contiguous:
+            raise RenderError(_capi.RTW_E_INVALID, "sums must be a contiguous float64 array [H, W, 3]")
+        self._check(_lib.rtw_render_window(self.ctx, C.byref(cam.raw), C.c_uint64(seed), first, n,
+                                           sums.ctypes.data_as(_capi._f64p), C.byref(self.stats)),
+                    "rtw_render_window")
+        return sums
+
+    def render_window_device(self, cam: Camera, seed: int, first: int, n: int, accum_ptr: int,
+                             accum_bytes: int, *, rank: int = 0, nranks: int = 1, stream: int | None = None):
+        """Asynchronous window [first, first + n) of this rank's tiles folded
+        onto a device accumulator of tiles_for_rank * 64 * 3 float64, packed
+        like render_device's output (rtw_render_window_device); on torch's
+        current stream by default."""
+        if stream is None:
+            stream = _torch_stream(self.device)
+        self._check(_lib.rtw_render_window_device(self.ctx, C.byref(cam.raw), C.c_uint64(seed), rank, nranks,
+                                                  first, n, C.c_void_p(accum_ptr) if accum_ptr else None,
+                                                  accum_bytes, C.c_void_p(stream) if stream else None),
+                    "rtw_render_window_device")
 
     def render_image_device(self, cam: Camera, seed: int, image_ptr: int, image_bytes: int, *,
                             stream: int | None = None):

@@ -44,6 +44,7 @@ void rtw_destroy(rtw_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->d_scene) (void)hipFree(c->d_scene);
     if (c->d_partial) (void)hipFree(c->d_partial);
+    if (c->d_accum) (void)hipFree(c->d_accum);
     if (c->d_out) (void)hipFree(c->d_out);
     if (c->d_img) (void)hipFree(c->d_img);
     if (c->d_counters) (void)hipFree(c->d_counters);
@@ -74,8 +75,13 @@ int rtw_set_tuning(rtw_ctx* c, const char* key, int64_t value) {
     const int prc = on_peers(c, [&](rtw_ctx* pk) { return rtw_set_tuning(pk, key, value); });
     if (prc) return prc;
     const std::string k = key;
-    if (value < 0) return fail(c, RTW_E_INVALID, "negative tuning value");
     rtw::RenderKnobs& t = c->knobs;
+    if (k == "window") {   // the one key with a negative value: -1 = auto
+        if (value < rtw::RenderKnobs::kWindowAuto) return fail(c, RTW_E_INVALID, "window: -1 (auto), 0 (off) or a sample count");
+        t.window = std::min<int64_t>(value, 0xFFFFFFFFll);
+        return RTW_OK;
+    }
+    if (value < 0) return fail(c, RTW_E_INVALID, "negative tuning value");
     if (k == "chunk") t.chunk = (uint32_t)value;
     else if (k == "auto_chunk") t.auto_chunk = std::max<uint32_t>(1, (uint32_t)value);
     else if (k == "robust") t.robust = (int)std::min<int64_t>(value, 2);

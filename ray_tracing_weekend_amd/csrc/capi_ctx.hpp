@@ -109,6 +109,8 @@ struct rtw_ctx {
     // work buffers
     void* d_partial = nullptr;
     size_t partial_cap = 0;
+    void* d_accum = nullptr;      // sample windows: the f64 running sums of this rank's packed tiles
+    size_t accum_cap = 0;
     void* d_out = nullptr;        // rtw_render: the packed tiles, then the image
     size_t out_cap = 0;
     void* d_img = nullptr;

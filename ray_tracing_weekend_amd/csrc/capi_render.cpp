@@ -75,6 +75,35 @@ int launch_render(const rtw::KParams<R>& p, const rtw::RenderPlan& pl, R* out, h
     else return rtw::launch_render_f64(p, pl.world, pl.launch_lds, out, stream, mid);
 }
 
+// a sample window: the render kernel, then the fold onto accum (out may be null)
+template <typename R>
+int launch_window(const rtw::KParams<R>& p, const rtw::RenderPlan& pl, double* accum, uint32_t first, R* out,
+                  hipStream_t stream, hipEvent_t mid) {
+    if constexpr (std::is_same<R, float>::value)
+        return rtw::launch_render_window_f32(p, pl.world, pl.launch_lds, accum, first, out, stream, mid);
+    else return rtw::launch_render_window_f64(p, pl.world, pl.launch_lds, accum, first, out, stream, mid);
+}
+
+// the device's memory, asked once (plan_chunk / plan_windows budget)
+size_t device_total(rtw_ctx* c) {
+    if (!c->dev_total) {
+        size_t fr = 0, tot = 0;
+        if (hipMemGetInfo(&fr, &tot) == hipSuccess) c->dev_total = tot;
+    }
+    return c->dev_total;
+}
+
+// One pass of a render: every sample of the camera (the one-shot render), or
+// the window [first, first + n) folded onto `accum`.
+struct Pass {
+    uint32_t first = 0, n = 0;
+    uint32_t chunk = 0;               // window passes: the samples per item (fixed for the render)
+    double* accum = nullptr;          // non-null: a window pass
+    bool begin = true;                // the first pass of a render: counters and stats start here
+    const rtw_camera* key_cam = nullptr;   // the camera of the task-order key: the same for every
+                                           // window of a render
+};
+
 // The tile costs counted by the last counting render (lpt.pending) -> lpt.h_cost
 // (waits for that render: once per key)
 int lpt_readback(rtw_ctx* c, uint32_t nt) {
@@ -109,6 +138,7 @@ int lpt_pilot(rtw_ctx* c, const rtw::KParams<R>& p, const rtw::RenderPlan& pl, h
     q.n_groups = 1;
     q.n_tasks = nt;
     q.seed = p.seed ^ 0x5851F42D4C957F2Dull;
+    q.s_base = q.c_base = 0;      // (its own samples: only their costs matter)
     q.task_table = nullptr;
     const size_t words = align_up((size_t)nt, 64);
     const size_t tile_bytes = (size_t)nt * 64 * 3 * sizeof(R);
@@ -226,16 +256,15 @@ int lpt_counted(rtw_ctx* c, const LptKey& key, hipStream_t stream) {
 // the device cannot hold it (other allocations) an auto chunk doubles instead
 // of failing -- stats.chunk reports it, the fold is then chunk-associated
 // (rounding level)
+// (fixed_chunk > 0, a window pass: that chunk or an error -- the windows of a
+// render share one fold association)
 template <typename R>
 int plan_and_allocate(rtw_ctx* c, const rtw::DevScene<R>& sc, const rtw_camera* cam, uint32_t n_local_tiles,
-                      rtw::RenderPlan* pl) {
+                      rtw::RenderPlan* pl, uint32_t fixed_chunk = 0) {
     const uint32_t spp = cam->samples_per_pixel;
-    if (!c->knobs.chunk && spp && !c->dev_total) {
-        size_t fr = 0, tot = 0;
-        if (hipMemGetInfo(&fr, &tot) == hipSuccess) c->dev_total = tot;
-    }
+    if (!c->knobs.chunk && spp) (void)device_total(c);
     const size_t per_chunk = (size_t)n_local_tiles * 64 * 3 * sizeof(R);
-    uint32_t chunk = rtw::plan_chunk<R>(c->knobs, spp, n_local_tiles, c->dev_total);
+    uint32_t chunk = fixed_chunk ? fixed_chunk : rtw::plan_chunk<R>(c->knobs, spp, n_local_tiles, c->dev_total);
     for (;;) {
         *pl = rtw::plan_render<R>(c->knobs, sc, *cam, n_local_tiles, chunk, c->scale);
         const size_t bytes = std::max<size_t>((size_t)pl->n_chunks * per_chunk, 64);
@@ -247,19 +276,26 @@ int plan_and_allocate(rtw_ctx* c, const rtw::DevScene<R>& sc, const rtw_camera* 
         if (e == hipSuccess) { c->partial_cap = bytes; break; }
         c->d_partial = nullptr;
         (void)hipGetLastError();
-        if (c->knobs.chunk || chunk >= spp || e != hipErrorOutOfMemory) return hip_fail(c, e, "hipMalloc(chunk sums)");
+        if (c->knobs.chunk || fixed_chunk || chunk >= spp || e != hipErrorOutOfMemory)
+            return hip_fail(c, e, "hipMalloc(chunk sums)");
         chunk = std::min<uint32_t>(chunk * 2, spp);
     }
     return pl->err ? fail(c, pl->err, pl->err_text) : RTW_OK;
 }
 
+// (a window pass writes d_out only when it is given: the render's last window)
 template <typename R>
-int render_device_t(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t rank, uint32_t nranks,
-                    void* d_out, size_t out_bytes, hipStream_t stream) {
+int render_pass_t(rtw_ctx* c, const rtw_camera* cam_in, uint64_t seed, uint32_t rank, uint32_t nranks,
+                  void* d_out, size_t out_bytes, hipStream_t stream, const Pass& pass) {
+    // the plan and the kernel see the pass's samples; their RNG streams start at s_base
+    rtw_camera pass_cam = *cam_in;
+    pass_cam.samples_per_pixel = pass.n;
+    const rtw_camera* cam = &pass_cam;
     rtw::KParams<R> p{};
     p.sc = *reinterpret_cast<const rtw::DevScene<R>*>(
         std::is_same<R, float>::value ? (const void*)&c->sc32 : (const void*)&c->sc64);
     fill_camera(p, cam);
+    p.s_base = pass.first;   // (c_base: once the chunk is planned)
     // the kernel holds a lane's pixel as i | j << 16
     if (p.W > 65535 || p.H > 65535) return fail(c, RTW_E_UNSUPPORTED, "image width or height beyond 65535");
     p.seed = seed;
@@ -268,8 +304,10 @@ int render_device_t(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t r
     p.tiles_x = rtw::tiles_across(p.W);
     p.n_local_tiles = rtw::tiles_for_rank(p.W, p.H, rank, nranks);
     const size_t need_out = (size_t)p.n_local_tiles * 64 * 3 * sizeof(R);
-    if (out_bytes < need_out) return fail(c, RTW_E_INVALID, "d_out is smaller than tiles_for_rank*64*3");
-    if (need_out && !d_out) return fail(c, RTW_E_INVALID, "d_out is NULL");
+    if (!pass.accum || d_out) {
+        if (out_bytes < need_out) return fail(c, RTW_E_INVALID, "d_out is smaller than tiles_for_rank*64*3");
+        if (need_out && !d_out) return fail(c, RTW_E_INVALID, "d_out is NULL");
+    }
     // the split's local -> global tile map (a dealt split; null: the round robin)
     const bool split = c->split.active(p.W, p.H, nranks);
     p.tile_map = nullptr;
@@ -279,9 +317,10 @@ int render_device_t(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t r
         p.tile_map = reinterpret_cast<const uint32_t*>(c->split.d_tile_map);
     }
     rtw::RenderPlan pl;
-    int rc = plan_and_allocate<R>(c, p.sc, cam, p.n_local_tiles, &pl);
+    int rc = plan_and_allocate<R>(c, p.sc, cam, p.n_local_tiles, &pl, pass.accum ? pass.chunk : 0u);
     if (rc) return rc;
     p.chunk = pl.chunk;
+    p.c_base = p.s_base / std::max(pl.chunk, 1u);
     p.n_chunks = pl.n_chunks;
     p.group = pl.group;
     p.n_groups = pl.n_groups;
@@ -299,18 +338,26 @@ int render_device_t(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t r
     p.tile_cost = nullptr;
     p.cost_spp = 0;
     p.cost_time = 0;
-    HIP_TRY(c, hipMemsetAsync(c->d_counters, 0, rtw_ctx::kCounters * sizeof(unsigned long long), stream));
-    const LptKey key = lpt_key(c, cam, rank, nranks);
+    if (pass.begin) {
+        HIP_TRY(c, hipMemsetAsync(c->d_counters, 0, rtw_ctx::kCounters * sizeof(unsigned long long), stream));
+    } else {
+        // a later window of the same render: the counters go on, but the task counter starts over
+        HIP_TRY(c, hipMemsetAsync(c->d_counters + 6, 0, sizeof(unsigned long long), stream));
+    }
+    const LptKey key = lpt_key(c, pass.key_cam ? pass.key_cam : cam_in, rank, nranks);
     if (pl.lpt) {
         rc = lpt_prepare(c, p, pl, key, split, stream);
         if (rc) return rc;
     }
     hipEvent_t* ev = c->ring[c->n_renders % rtw_ctx::kRing];
-    HIP_TRY(c, hipEventRecord(c->ev0, stream));
+    if (pass.begin) HIP_TRY(c, hipEventRecord(c->ev0, stream));
     HIP_TRY(c, hipEventRecord(ev[0], stream));
     int lrc = 0;
     if (need_out == 0) {
         HIP_TRY(c, hipEventRecord(ev[1], stream));
+    } else if (pass.accum) {
+        if (p.max_depth == 0) p.n_tasks = p.n_chunks = 0;   // every sample is 0: the fold alone
+        lrc = launch_window(p, pl, pass.accum, pass.first, reinterpret_cast<R*>(d_out), stream, ev[1]);
     } else if (p.spp == 0 || p.max_depth == 0) {
         // depth == 0: every sample is Colour::default() + res = 0 (camera.rs:470-472)
         HIP_TRY(c, hipMemsetAsync(d_out, 0, need_out, stream));
@@ -329,8 +376,9 @@ int render_device_t(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t r
     ++c->n_renders;
     std::vector<uint32_t> tiles;
     c->split.local_tiles(p.W, p.H, rank, nranks, tiles);
+    const uint64_t before = pass.begin ? 0 : c->last.samples;
     c->last = rtw_stats{};
-    c->last.samples = rtw::tile_pixels(p.W, p.H, tiles) * p.spp;
+    c->last.samples = before + rtw::tile_pixels(p.W, p.H, tiles) * p.spp;
     c->last.accel = (uint32_t)pl.accel;
     c->last.bvh_width = pl.bvh_width;
     c->last.kernel = (uint32_t)pl.world;
@@ -339,6 +387,82 @@ int render_device_t(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t r
     c->last_n_list = p.sc.n_list;
     c->last.chunk = pl.chunk;
     return RTW_OK;
+}
+
+// this context's f64 accumulator of window renders: n_local_tiles * 64 * 3 doubles
+int ensure_accum(rtw_ctx* c, uint32_t n_local_tiles) {
+    return ensure(c, &c->d_accum, &c->accum_cap, std::max<size_t>((size_t)n_local_tiles * 64 * 3 * sizeof(double), 64));
+}
+
+// A render of this rank's tiles: one pass, or (tuning "window") the windows of
+// plan_windows one after another on `stream`, folded onto the context's
+// accumulator; the last one writes d_out.
+template <typename R>
+int render_device_t(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t rank, uint32_t nranks,
+                    void* d_out, size_t out_bytes, hipStream_t stream) {
+    Pass one;
+    one.n = cam->samples_per_pixel;
+    if (c->knobs.window == 0) return render_pass_t<R>(c, cam, seed, rank, nranks, d_out, out_bytes, stream, one);
+    const uint32_t nt = rtw::tiles_for_rank(cam->image_width, cam->image_height, rank, nranks);
+    const rtw::WindowPlan w = rtw::plan_windows<R>(c->knobs, cam->samples_per_pixel, nt, device_total(c));
+    if (w.n_windows <= 1 || nt == 0) return render_pass_t<R>(c, cam, seed, rank, nranks, d_out, out_bytes, stream, one);
+    if (out_bytes < (size_t)nt * 64 * 3 * sizeof(R)) return fail(c, RTW_E_INVALID, "d_out is smaller than tiles_for_rank*64*3");
+    if (!d_out) return fail(c, RTW_E_INVALID, "d_out is NULL");
+    int rc = ensure_accum(c, nt);
+    if (rc) return rc;
+    for (uint32_t k = 0; k < w.n_windows; ++k) {
+        Pass ps;
+        ps.first = k * w.window;
+        ps.n = std::min(w.window, cam->samples_per_pixel - ps.first);
+        ps.chunk = w.chunk;   // (not clamped to a short last window: s_base stays a multiple of it)
+        ps.accum = reinterpret_cast<double*>(c->d_accum);
+        ps.begin = k == 0;
+        ps.key_cam = cam;
+        const bool last = k + 1 == w.n_windows;
+        rc = render_pass_t<R>(c, cam, seed, rank, nranks, last ? d_out : nullptr, last ? out_bytes : 0, stream, ps);
+        if (rc) return rc;
+    }
+    return RTW_OK;
+}
+
+// The samples per item of a window of n samples (rtw_render_window_device);
+// windows continue each other only when they start on an item boundary.
+template <typename R>
+uint32_t window_chunk(rtw_ctx* c, uint32_t n, uint32_t nt) {
+    return c->knobs.chunk ? c->knobs.chunk : rtw::plan_chunk<R>(c->knobs, n, nt, device_total(c));
+}
+
+// rtw_render_window_device's arguments (nothing is launched)
+template <typename R>
+int check_window(rtw_ctx* c, const rtw_camera* cam, uint32_t rank, uint32_t nranks, uint32_t first, uint32_t n,
+                 const double* d_accum, size_t accum_bytes) {
+    const uint32_t nt = rtw::tiles_for_rank(cam->image_width, cam->image_height, rank, nranks);
+    const uint32_t chunk = window_chunk<R>(c, n, nt);
+    if (first % chunk)
+        return fail(c, RTW_E_INVALID, "first_sample is not a multiple of the chunk (" + std::to_string(chunk) + ")");
+    if (accum_bytes < (size_t)nt * 64 * 3 * sizeof(double))
+        return fail(c, RTW_E_INVALID, "d_accum is smaller than tiles_for_rank*64*3 doubles");
+    if (nt && !d_accum) return fail(c, RTW_E_INVALID, "d_accum is NULL");
+    return RTW_OK;
+}
+
+// rtw_render_window_device on a one-device context, its arguments checked
+template <typename R>
+int render_window_t(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t rank, uint32_t nranks,
+                    uint32_t first, uint32_t n, double* d_accum, hipStream_t stream) {
+    const uint32_t nt = rtw::tiles_for_rank(cam->image_width, cam->image_height, rank, nranks);
+    const uint32_t chunk = window_chunk<R>(c, n, nt);
+    // the task-order key of a window render: the camera without its sample count
+    rtw_camera key_cam = *cam;
+    key_cam.samples_per_pixel = 0;
+    Pass ps;
+    ps.first = first;
+    ps.n = n;
+    ps.chunk = chunk;
+    ps.accum = d_accum;
+    ps.key_cam = &key_cam;
+    if (nt == 0) ps.accum = nullptr;   // nothing to fold: the bookkeeping of an empty render
+    return render_pass_t<R>(c, cam, seed, rank, nranks, nullptr, 0, stream, ps);
 }
 
 }  // namespace
@@ -409,6 +533,73 @@ int rtw_render_device(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t
     }
     return c->precision == RTW_F32 ? render_device_t<float>(c, cam, seed, rank, nranks, d_out, out_bytes, s)
                                    : render_device_t<double>(c, cam, seed, rank, nranks, d_out, out_bytes, s);
+}
+
+int rtw_render_window_device(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t rank, uint32_t nranks,
+                             uint32_t first_sample, uint32_t n_samples, double* d_accum, size_t accum_bytes,
+                             void* stream) {
+    if (!c || !cam || nranks == 0 || rank >= nranks) return fail(c, RTW_E_INVALID, "bad argument");
+    if (c->multi) return fail(c, RTW_E_UNSUPPORTED, "sample windows of a multi-device context: tuning \"window\"");
+    if (!c->has_scene) return fail(c, RTW_E_NO_SCENE, "rtw_set_scene was not called");
+    if ((uint64_t)first_sample + n_samples > 0xFFFFFFFFull)
+        return fail(c, RTW_E_INVALID, "first_sample + n_samples overflows");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int rc = c->precision == RTW_F32
+                       ? check_window<float>(c, cam, rank, nranks, first_sample, n_samples, d_accum, accum_bytes)
+                       : check_window<double>(c, cam, rank, nranks, first_sample, n_samples, d_accum, accum_bytes);
+    if (rc || n_samples == 0) return rc;
+    hipStream_t s = resolve_stream(c, stream);
+    c->stats_ranks = 1;
+    return c->precision == RTW_F32
+               ? render_window_t<float>(c, cam, seed, rank, nranks, first_sample, n_samples, d_accum, s)
+               : render_window_t<double>(c, cam, seed, rank, nranks, first_sample, n_samples, d_accum, s);
+}
+
+int rtw_render_window(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t first_sample, uint32_t n_samples,
+                      double* sums, rtw_stats* stats) {
+    if (!c || !cam || !sums) return fail(c, RTW_E_INVALID, "bad argument");
+    if (c->multi) return fail(c, RTW_E_UNSUPPORTED, "sample windows of a multi-device context: tuning \"window\"");
+    const uint32_t W = cam->image_width, H = cam->image_height;
+    HIP_TRY(c, hipSetDevice(c->device));
+    std::vector<uint32_t> tiles;   // the packed order of the one rank's tiles (host/tiles.hpp)
+    c->split.local_tiles(W, H, 0, 1, tiles);
+    const size_t n = tiles.size() * 64 * 3;
+    int rc = ensure_accum(c, (uint32_t)tiles.size());
+    if (rc) return rc;
+    const uint32_t tiles_x = rtw::tiles_across(W);
+    // image [H][W][3] <-> packed tiles [lt][ly * 8 + lx][3]
+    auto each_pixel = [&](auto&& f) {
+        for (size_t lt = 0; lt < tiles.size(); ++lt) {
+            const uint32_t tx = tiles[lt] % tiles_x, ty = tiles[lt] / tiles_x;
+            for (uint32_t px = 0; px < 64; ++px) {
+                const uint32_t i = tx * rtw::kTile + (px & 7u), j = ty * rtw::kTile + (px >> 3);
+                if (i < W && j < H) f(((size_t)j * W + i) * 3, (lt * 64 + px) * 3);
+            }
+        }
+    };
+    std::vector<double> packed(n, 0.0);
+    if (first_sample && n_samples && n) {
+        each_pixel([&](size_t img, size_t pk) {
+            for (int k = 0; k < 3; ++k) packed[pk + k] = sums[img + k];
+        });
+        HIP_TRY(c, hipMemcpyAsync(c->d_accum, packed.data(), n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
+    rc = rtw_render_window_device(c, cam, seed, 0, 1, first_sample, n_samples, reinterpret_cast<double*>(c->d_accum),
+                                  c->accum_cap, nullptr);
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);   // (the upload reads `packed`)
+        return rc;
+    }
+    if (n_samples == 0) return RTW_OK;
+    if (n) HIP_TRY(c, hipMemcpyAsync(packed.data(), c->d_accum, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    each_pixel([&](size_t img, size_t pk) {
+        for (int k = 0; k < 3; ++k) sums[img + k] = packed[pk + k];
+    });
+    rtw_stats st{};
+    rc = rtw_get_stats(c, &st);
+    if (stats) *stats = st;
+    return rc;
 }
 
 int rtw_render(rtw_ctx* c, const rtw_camera* cam, const rtw_scene* scene, uint64_t seed, double* out_sum,

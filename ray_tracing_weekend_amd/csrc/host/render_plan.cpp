@@ -29,6 +29,41 @@ uint32_t plan_chunk(const RenderKnobs& k, uint32_t spp, uint32_t n_local_tiles, 
 }
 
 template <typename R>
+WindowPlan plan_windows(const RenderKnobs& k, uint32_t spp, uint32_t n_local_tiles, size_t dev_total) {
+    WindowPlan w;
+    const size_t per_chunk = (size_t)n_local_tiles * 64 * 3 * sizeof(R);
+    auto one_shot = [&]() {
+        w.chunk = plan_chunk<R>(k, spp, n_local_tiles, dev_total);
+        w.window = spp;
+        w.n_windows = spp ? 1 : 0;
+        w.partial_bytes = (size_t)(((uint64_t)spp + w.chunk - 1) / w.chunk) * per_chunk;
+        return w;
+    };
+    if (k.window == 0 || spp == 0) return one_shot();
+    uint64_t window = 0;
+    if (k.window > 0) {
+        window = (uint64_t)k.window;
+    } else {
+        // auto: the most chunks of the configured size that fit the budget plan_chunk keeps
+        const uint32_t chunk = std::max<uint32_t>(1, k.chunk ? k.chunk : k.auto_chunk);
+        size_t pmax = k.partial_max;
+        if (dev_total) pmax = std::min(pmax, dev_total / 2);
+        const size_t max_chunks = std::max<size_t>(1, pmax / std::max<size_t>(per_chunk, 1));
+        window = (uint64_t)std::min<size_t>(max_chunks, 0xFFFFFFFFu / chunk) * chunk;
+    }
+    if (window >= spp) return one_shot();
+    // the chunk of a window this long (auto: grows only when one window exceeds the budget)
+    // (an explicit chunk stays as it is: the window is rounded up to a multiple of it)
+    w.chunk = k.chunk ? k.chunk : plan_chunk<R>(k, (uint32_t)window, n_local_tiles, dev_total);
+    window = (window + w.chunk - 1) / w.chunk * w.chunk;
+    if (window >= spp) return one_shot();
+    w.window = (uint32_t)window;
+    w.n_windows = (uint32_t)(((uint64_t)spp + w.window - 1) / w.window);
+    w.partial_bytes = (size_t)(w.window / w.chunk) * per_chunk;
+    return w;
+}
+
+template <typename R>
 RenderPlan plan_render(const RenderKnobs& k, const DevScene<R>& sc, const rtw_camera& cam, uint32_t n_local_tiles,
                        uint32_t chunk, const SceneScale& scale) {
     RenderPlan p;
@@ -179,6 +214,8 @@ RenderPlan plan_render(const RenderKnobs& k, const DevScene<R>& sc, const rtw_ca
 
 template uint32_t plan_chunk<float>(const RenderKnobs&, uint32_t, uint32_t, size_t);
 template uint32_t plan_chunk<double>(const RenderKnobs&, uint32_t, uint32_t, size_t);
+template WindowPlan plan_windows<float>(const RenderKnobs&, uint32_t, uint32_t, size_t);
+template WindowPlan plan_windows<double>(const RenderKnobs&, uint32_t, uint32_t, size_t);
 template RenderPlan plan_render<float>(const RenderKnobs&, const DevScene<float>&, const rtw_camera&, uint32_t,
                                        uint32_t, const SceneScale&);
 template RenderPlan plan_render<double>(const RenderKnobs&, const DevScene<double>&, const rtw_camera&, uint32_t,

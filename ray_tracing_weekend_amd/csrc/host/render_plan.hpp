@@ -87,6 +87,11 @@ struct RenderKnobs {
     uint32_t cost_time = 1;           // tile costs in wave-time shares (KParams::cost_time); 0: work counts
     uint64_t guide_floor = 1u << 20;
     uint32_t balance = 1;             // multi-device renders: deal tiles by their counted costs
+    static constexpr int64_t kWindowAuto = -1;
+    int64_t window = 0;               // sample windows (plan_windows): 0 off; N > 0: renders of more
+                                      // than N samples per pixel run N at a time onto an f64
+                                      // accumulator; kWindowAuto: the largest window whose chunk
+                                      // sums fit partial_max
 };
 
 // What plan_render decides.  err != RTW_OK: no render (err_text says why);
@@ -114,6 +119,20 @@ struct RenderPlan {
 // device's memory, 0: unknown).
 template <typename R>
 uint32_t plan_chunk(const RenderKnobs& k, uint32_t spp, uint32_t n_local_tiles, size_t dev_total);
+
+// Step 1 with sample windows (knobs.window): a render of spp samples runs as
+// n_windows windows of `window` samples (a multiple of the chunk; the last may
+// be short), each folded onto an f64 accumulator, so the chunk sums hold one
+// window: partial_bytes = ceil(window / chunk) * n_local_tiles * 64 * 3 *
+// sizeof(R).  knobs.window 0: one window of spp samples at plan_chunk's chunk
+// (the one-shot render).  In window mode the auto chunk is sized against the
+// window, never against spp: with kWindowAuto it stays auto_chunk at any spp.
+struct WindowPlan {
+    uint32_t chunk = 1, window = 0, n_windows = 0;
+    size_t partial_bytes = 0;
+};
+template <typename R>
+WindowPlan plan_windows(const RenderKnobs& k, uint32_t spp, uint32_t n_local_tiles, size_t dev_total);
 
 // Step 2: everything else, for the chunk that was actually allocated.
 template <typename R>

@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include <array>
+#include <functional>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -228,6 +229,16 @@ class Camera {
                                                          const RenderOptions& opt = {}) const {
         return render(world, lights, opt);
     }
+    // The same render `window` samples at a time (rtw_render_window on one
+    // device; opt.device_mask is not used): after each window on_window(samples
+    // done, the running sums [H][W][3], j = 0 the bottom row) is called; false
+    // from it stops the render there.  Returns the sums so far as render()
+    // does -- after the last window render()'s image bit for bit.  Defined in
+    // host/render_windows.cpp.
+    std::vector<std::vector<SampledColour>> render_windows(
+        const HittableList& world, const HittableList& lights, uint32_t window,
+        const std::function<bool(uint32_t, const std::vector<double>&)>& on_window,
+        const RenderOptions& opt = {}) const;
     const rtw_camera& raw() const { return c_; }
 
    private:

@@ -668,7 +668,10 @@ __global__ void __launch_bounds__((64 * kernel_waves<R, kWorld, kOpt>()), (kerne
     // the wave's current task (wave-uniform): local tile lt = global 8x8 tile
     // T = lt * nranks + rank at (tx, ty) -- the ranks take the image's tiles
     // round-robin (rtw_tiles_for_rank) -- and chunks [c_begin, c_begin +
-    // glen): a pool of 64 glen (pixel, chunk) items
+    // glen): a pool of 64 glen (pixel, chunk) items.  Chunk indices are absolute:
+    // a sample window's start at c_base (KParams::c_base, added once per task), so
+    // a lane's c and s = c * chunk + ... are the render's own chunk and sample
+    // indices and a sample's start costs a window nothing
     uint32_t lt = 0, tx = 0, ty = 0, c_begin = 0, glen = 0;
     uint32_t glen_m = 0;          // glen > 1: ceil(2^32 / glen), q / glen = umulhi(q, glen_m) for q < 64 glen
                                   // (2^32 does not fit: glen == 1 is special-cased)
@@ -699,13 +702,14 @@ __global__ void __launch_bounds__((64 * kernel_waves<R, kWorld, kOpt>()), (kerne
         if (k->task_table) {   // longest tiles first, cut by cost
             lt = k->task_table[2 * t];
             const uint32_t e = k->task_table[2 * t + 1];
-            c_begin = e & 0xFFFFFu;
+            c_begin = (e & 0xFFFFFu) + k->c_base;
             glen = e >> 20;
         } else {
             lt = t / k->n_groups;
             const uint32_t cg = t - lt * k->n_groups;
             c_begin = cg * k->group;
             glen = min(c_begin + k->group, k->n_chunks) - c_begin;
+            c_begin += k->c_base;
         }
         const uint32_t T = k->tile_map ? k->tile_map[lt] : lt * k->nranks + k->rank;   // (global_tile)
         ty = T / k->tiles_x;
@@ -1627,6 +1631,77 @@ __global__ void __launch_bounds__(64) reduce_chunks_kernel(const KParams<R> p, R
     dst[0] = (R)sx;
     dst[1] = (R)sy;
     dst[2] = (R)sz;
+}
+
+// The continuing form of reduce_chunks_kernel (sample windows, KParams::s_base):
+// each pixel's running sum starts from accum[(lt * 64 + px) * 3] -- the sums of
+// the samples before the window, always f64: an f32 carry would round between
+// windows, the one-shot fold rounds once -- or from 0 when `first_sample` is 0
+// (accum's contents are then ignored), takes the window's chunk sums in chunk
+// order and goes back to accum; `out` (may be null) also receives it rounded to
+// R, the packed tiles of reduce_chunks_kernel.  Windows of a render folded one
+// after another are the one-shot fold at the same chunk, addition by addition.
+template <typename R>
+__global__ void __launch_bounds__(64) fold_window_kernel(const KParams<R> p, double* __restrict__ accum,
+                                                         uint32_t first_sample, R* __restrict__ out) {
+    constexpr uint32_t kFoldWin = kFoldWindow<R>;
+    constexpr uint32_t kFoldRow = kFoldWin * 3 + 1;    // LDS row (odd: no bank conflicts)
+    __shared__ R win[64 * kFoldRow];
+    const uint32_t lt = blockIdx.x, lane = threadIdx.x;
+    const uint32_t T = global_tile(p, lt);
+    const uint32_t ty = T / p.tiles_x, tx = T - ty * p.tiles_x;
+    const uint32_t i = tx * kTile + (lane & 7), j = ty * kTile + (lane >> 3);
+    const size_t row_len = (size_t)p.n_chunks * 3;
+    const R* tile = p.partial + (size_t)lt * 64 * row_len;
+    double* acc = accum + ((size_t)lt * 64 + lane) * 3;
+    double sx = 0, sy = 0, sz = 0;
+    if (first_sample) {
+        sx = acc[0];
+        sy = acc[1];
+        sz = acc[2];
+    }
+    constexpr uint32_t kNv = kFoldWin * 3;
+    for (uint32_t c0 = 0; c0 < p.n_chunks; c0 += kFoldWin) {
+        const uint32_t kw = min(kFoldWin, p.n_chunks - c0), nv = kw * 3;
+        const R* src = tile + (size_t)c0 * 3;
+        if (kw == kFoldWin) {
+            // full pass: every lane's kNv loads issued back to back (as reduce_chunks_kernel)
+            R v[kNv];
+#pragma unroll
+            for (uint32_t it = 0; it < kNv; ++it) {
+                const uint32_t idx = it * 64 + lane, r = idx / kNv, col = idx - r * kNv;
+                v[it] = src[r * row_len + col];
+            }
+#pragma unroll
+            for (uint32_t it = 0; it < kNv; ++it) {
+                const uint32_t idx = it * 64 + lane, r = idx / kNv, col = idx - r * kNv;
+                win[r * kFoldRow + col] = v[it];
+            }
+        } else {
+            for (uint32_t idx = lane; idx < 64 * nv; idx += 64) {
+                const uint32_t r = idx / nv, col = idx - r * nv;
+                win[r * kFoldRow + col] = src[r * row_len + col];
+            }
+        }
+        __syncthreads();
+        const R* row = win + lane * kFoldRow;
+        for (uint32_t k = 0; k < kw; ++k) {
+            sx = sx + (double)row[3 * k];
+            sy = sy + (double)row[3 * k + 1];
+            sz = sz + (double)row[3 * k + 2];
+        }
+        __syncthreads();
+    }
+    if (i >= p.W || j >= p.H) sx = sy = sz = 0;   // never written
+    acc[0] = sx;
+    acc[1] = sy;
+    acc[2] = sz;
+    if (out) {
+        R* dst = out + ((size_t)lt * 64 + lane) * 3;
+        dst[0] = (R)sx;
+        dst[1] = (R)sy;
+        dst[2] = (R)sz;
+    }
 }
 
 // Un-interleave the ranks' packed tiles into the image [H][W][3]: one thread

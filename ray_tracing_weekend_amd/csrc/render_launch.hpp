@@ -137,10 +137,15 @@ inline int launch_lgrid_impl(const KParams<R>& p, int world, size_t lds_bytes, h
 // Options per launch: the f32 sphere-test form (DevScene::robust; f64 keeps
 // the reference arithmetic only) and the light BVH (KParams::light_bvh).
 // Returns the variant that ran (launch_world's code; 0: no launch), or -1.
+// `accum` non-null: a sample window -- fold_window_kernel onto accum (read when
+// first_sample > 0; out may then be null) instead of the chunk reduction.
 template <typename R>
-inline int launch_render_impl(const KParams<R>& p, int world, size_t lds_bytes, R* out,
-                              hipStream_t stream, hipEvent_t mid) {
+inline int launch_render_impl(const KParams<R>& p_in, int world, size_t lds_bytes, R* out,
+                              hipStream_t stream, hipEvent_t mid, double* accum = nullptr,
+                              uint32_t first_sample = 0) {
     int ran = 0;
+    // (a window: the render kernel's absolute view; the fold below reads p_in)
+    const KParams<R> p = render_kernel_view(p_in);
     if (p.n_tasks) {
         const bool robust = sizeof(R) == 4 && p.sc.robust;
         const bool lbvh = p.light_bvh != 0;
@@ -194,8 +199,12 @@ inline int launch_render_impl(const KParams<R>& p, int world, size_t lds_bytes, 
         if (hipGetLastError() != hipSuccess) return -1;
     }
     if (mid && hipEventRecord(mid, stream) != hipSuccess) return -1;
-    if (p.n_local_tiles) {
-        hipLaunchKernelGGL((dev::reduce_chunks_kernel<R>), dim3(p.n_local_tiles), dim3(64), 0, stream, p,
+    if (p_in.n_local_tiles && accum) {
+        hipLaunchKernelGGL((dev::fold_window_kernel<R>), dim3(p_in.n_local_tiles), dim3(64), 0, stream, p_in,
+                           accum, first_sample, out);
+        if (hipGetLastError() != hipSuccess) return -1;
+    } else if (p_in.n_local_tiles) {
+        hipLaunchKernelGGL((dev::reduce_chunks_kernel<R>), dim3(p_in.n_local_tiles), dim3(64), 0, stream, p_in,
                            out);
         if (hipGetLastError() != hipSuccess) return -1;
     }

@@ -304,7 +304,30 @@ struct KParams {
                                       // walk (lights_pdf_grid_coop); 0: one lane per ray
     const uint32_t* tile_map;         // non-null: local tile lt -> global tile (a dealt split,
                                       // rtw_set_split); null: lt * nranks + rank (the round robin)
+    // Sample window (0, 0: a one-shot render): s_base is the absolute index of its
+    // first sample, a multiple of the chunk, c_base = s_base / chunk its first
+    // chunk.  The host fills spp, n_chunks, cost_spp and partial window-local
+    // (the fold kernels read them so); the render kernel works on the render's
+    // absolute chunk and sample indices -- it adds c_base to a task's first chunk,
+    // so the RNG stream of a sample is that of s_base + its local index at no
+    // cost per sample -- and is launched with render_kernel_view's copy.
+    uint32_t s_base, c_base;
 };
+
+// What the render kernel is launched with: spp and cost_spp as absolute sample
+// bounds, partial moved back by c_base chunks, so that the absolute chunk c of a
+// pixel lands in the window's slot c - c_base (the kernel addresses
+// partial[(slot * n_chunks + c) * 3]; no element before the buffer is touched).
+template <typename R>
+inline KParams<R> render_kernel_view(const KParams<R>& p) {
+    KParams<R> q = p;
+    if (p.s_base) {
+        q.spp = p.s_base + p.spp;
+        q.cost_spp = p.s_base + p.cost_spp;
+        q.partial = reinterpret_cast<R*>(reinterpret_cast<uintptr_t>(p.partial) - (uintptr_t)p.c_base * 3 * sizeof(R));
+    }
+    return q;
+}
 
 // the global 8x8 tile of local tile lt
 template <typename R>
@@ -326,6 +349,14 @@ int launch_render_f32(const KParams<float>& p, int world, size_t lds_bytes, floa
                       hipStream_t stream, hipEvent_t mid);
 int launch_render_f64(const KParams<double>& p, int world, size_t lds_bytes, double* out,
                       hipStream_t stream, hipEvent_t mid);
+// A sample window: the render kernel (p.s_base = the window's first sample,
+// p.spp its length), then fold_window_kernel instead of the chunk reduction --
+// onto accum (n_local_tiles * 64 * 3 doubles; read when first_sample > 0) and,
+// when out is non-null, rounded to R into out.  p.n_tasks 0: the fold alone.
+int launch_render_window_f32(const KParams<float>& p, int world, size_t lds_bytes, double* accum,
+                             uint32_t first_sample, float* out, hipStream_t stream, hipEvent_t mid);
+int launch_render_window_f64(const KParams<double>& p, int world, size_t lds_bytes, double* accum,
+                             uint32_t first_sample, double* out, hipStream_t stream, hipEvent_t mid);
 // The ranks' packed tiles (nranks buffers, rank_stride elements apart) -> the
 // image [H][W][3] (rtw_assemble_tiles).  slot (may be null: the round robin,
 // T itself): global tile T -> lt * nranks + rank of a dealt split.
