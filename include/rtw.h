@@ -51,6 +51,27 @@ extern "C" {
 #define RTW_F32 0                /* speed mode: f32 + FMA + native sqrt/rcp/sin/cos */
 #define RTW_F64 1                /* parity mode: f64, no FMA contraction, same op order
                                     as the reference (bit-comparable with the oracle) */
+/* Supported range of the parity mode.  Its kernels cull candidates with f32
+ * filters (a widened slab test, pre-passes before the f64 sphere and light
+ * tests, an f32 walk of the light grid) that must never drop what the f64 test
+ * accepts.  What is tested, with zero exceptions allowed:
+ *   - whole renders, the light grid's walk included: scenes and cameras scaled
+ *     by 2^-40 .. 2^40, translated by up to 2^22, focus_dist 2^-30 .. 2^30,
+ *     light queries from 10^4 away.  This is the supported range;
+ *   - the pre-passes and the slab tests alone, primitive by primitive: sizes
+ *     2^-130 .. 2^130 with |d| = 2^-30 .. 2^30 -- where a coordinate or its
+ *     square leaves f32's range they keep every candidate.  The light grid's
+ *     f32 walk does NOT fail open there (beyond f32 its box test is NaN and
+ *     the ray "misses the grid"), so whole renders beyond 2^+-40 are not
+ *     promised;
+ *   - a ray direction must keep d . d, its reciprocal and d . (o - c) normal
+ *     f32 numbers: |d|_1 within 2^-60 .. 2^46 (the reference never normalises
+ *     directions: a camera's primary rays have the length of focus_dist,
+ *     scattered rays about 1).  A camera scaled by 2^-70 (|d| = 2^-67) renders
+ *     wrong pixels: the leaf pre-pass drops spheres the reference hits;
+ *   - direction components that are exactly +-0 are fine in the parity mode.
+ *     The speed mode (RTW_F32) can lose boxes for a ray with a component
+ *     exactly 0 beside a non-zero origin component. */
 
 /* material kinds (shared/src/material.rs) */
 #define RTW_LAMBERTIAN 0         /* material.rs:327-376 (SolidColour texture) */

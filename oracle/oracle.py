@@ -147,6 +147,10 @@ def lib():
         L.rtwo_aabb_hit.argtypes = [_f64p, _f64p, _f64p, C.c_double, C.c_double]
         L.rtwo_sphere_pdf_value.argtypes = [_f64p, _f64p, _f64p]
         L.rtwo_sphere_pdf_value.restype = C.c_double
+        _i32p = C.POINTER(C.c_int)
+        L.rtwo_sphere_hit_batch.argtypes = [_f64p, C.c_uint32, C.c_double, C.c_double, _i32p, _f64p]
+        L.rtwo_sphere_pdf_value_batch.argtypes = [_f64p, C.c_uint32, _f64p]
+        L.rtwo_aabb_hit_batch.argtypes = [_f64p, C.c_uint32, _i32p]
         L.rtwo_onb.argtypes = [_f64p, _f64p, _f64p, _f64p]
         L.rtwo_reflectance.argtypes = [C.c_double, C.c_double]
         L.rtwo_reflectance.restype = C.c_double
@@ -459,6 +463,31 @@ def world_hit(sc: Scene, o, d, accel=ACCEL_BRUTE):
     k = lib().rtwo_world_hit(C.byref(s), accel, arr(o), arr(d), out)
     del keep
     return k, out[0], tuple(out[1:4]), tuple(out[4:7]), bool(out[7])
+
+
+# ---- batched primitives (tests/cull_cases.py)
+def sphere_hit_batch(rec, tmin=2.220446049250313e-16, tmax=float("inf")):
+    """rec (n, 10) {o, d, c, r} -> (hit[n] bool, t[n]) of rtwo_sphere_hit."""
+    rec = np.ascontiguousarray(rec, np.float64).reshape(-1, 10)
+    hit = np.zeros(len(rec), np.int32)
+    t = np.zeros(len(rec))
+    lib().rtwo_sphere_hit_batch(_p(rec, _f64p), len(rec), tmin, tmax, _p(hit, C.POINTER(C.c_int)), _p(t, _f64p))
+    return hit != 0, t
+
+
+def sphere_pdf_value_batch(rec):
+    rec = np.ascontiguousarray(rec, np.float64).reshape(-1, 10)
+    pdf = np.zeros(len(rec))
+    lib().rtwo_sphere_pdf_value_batch(_p(rec, _f64p), len(rec), _p(pdf, _f64p))
+    return pdf
+
+
+def aabb_hit_batch(rec):
+    """rec (n, 13) {o, d, box min, box max, tmax} -> hit[n] bool within [0, tmax]."""
+    rec = np.ascontiguousarray(rec, np.float64).reshape(-1, 13)
+    hit = np.zeros(len(rec), np.int32)
+    lib().rtwo_aabb_hit_batch(_p(rec, _f64p), len(rec), _p(hit, C.POINTER(C.c_int)))
+    return hit != 0
 
 
 # ---- texture KAT entry points

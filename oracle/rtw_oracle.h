@@ -206,6 +206,12 @@ int rtwo_plane_hit(const double pl[6], const double o[3], const double d[3],
 int rtwo_aabb_hit(const double box[6], const double o[3], const double d[3],
                   double tmin, double tmax);
 double rtwo_sphere_pdf_value(const double sph[4], const double o[3], const double d[3]);
+/* The three above over n records (loops, no arithmetic of their own).  Sphere
+ * records are {o xyz, d xyz, c xyz, r}; box records {o xyz, d xyz, min xyz,
+ * max xyz, tmax}, tested within [0, tmax]. */
+void rtwo_sphere_hit_batch(const double *rec, uint32_t n, double tmin, double tmax, int *hit, double *t);
+void rtwo_sphere_pdf_value_batch(const double *rec, uint32_t n, double *pdf);
+void rtwo_aabb_hit_batch(const double *rec, uint32_t n, int *hit);
 void rtwo_onb(const double n[3], double u[3], double v[3], double w[3]);
 double rtwo_reflectance(double cosine, double ref_idx);
 void rtwo_reflect(const double v[3], const double n[3], double out[3]);

@@ -157,6 +157,36 @@ struct SphereTester<float, kRobust> {    // the f32 sweep's arithmetic (see sphe
 
 __device__ __forceinline__ double inv_(double x) { return 1.0 / x; }
 __device__ __forceinline__ float inv_(float x) { return __builtin_amdgcn_rcpf(x); }
+// One axis of a ray for the slab tests t = b ix - o ix: ix = 1 / d and o ix.
+// f64: when o ix is not finite -- a zero direction component (ix = inf) -- the
+// two planes of a box come out as a signed infinity and inf - inf = NaN (a box
+// that straddles 0 with o beside 0: lo ix - o ix = -inf, hi ix - o ix = NaN),
+// and fmin / fmax, which drop the NaN, would keep the infinity for both the
+// near and the far plane: a box the ray passes through, culled.  Such an axis
+// gets ix = o ix = NaN: every plane NaN, dropped by fmin / fmax -- the slab
+// unbounded, which only ever keeps a box.  (The f32 speed mode keeps the plain
+// form and with it that corner -- a direction component exactly 0 beside a
+// non-zero origin component: its kernels are the parent's, instruction for
+// instruction; the guard in them measured -1.3 % on the f32 headline.)
+template <typename R>
+__device__ __forceinline__ void slab_axis(R o, R d, R& ix, R& oix) {
+    ix = inv_(d);
+    oix = o * ix;
+    if constexpr (sizeof(R) == 8) {
+        if (!(fabs(oix) < (R)INFINITY)) ix = oix = (R)NAN;
+    }
+}
+// The three axes of the while-while traversals' f32 slab tests: plain 1 / d
+// and o ix.  kWide (an f64 ray on the f32 tree): a non-finite o ix makes the
+// widening slack s = 2^-20 max |o ix| infinite, so an interval that the
+// inf - inf above spoils ends as tn - s = NaN or tf + s = NaN, which the
+// traversal's compare !(tn > tf) keeps: every box entered, correct and only
+// slow, with no work at the ray's setup (the f64 headline pays for any).
+__device__ __forceinline__ void ray_slabs(V3<float> o, V3<float> d, float& ix, float& iy, float& iz, float& oix,
+                                          float& oiy, float& oiz) {
+    ix = inv_(d.x), iy = inv_(d.y), iz = inv_(d.z);
+    oix = o.x * ix, oiy = o.y * iy, oiz = o.z * iz;
+}
 
 // Near-child-first traversal with a per-lane stack in LDS (stk[entry * 64]).
 // Slab test on padded child boxes against [0, tb].
@@ -165,8 +195,10 @@ __device__ __forceinline__ void bvh_traverse(const DevScene<R>& sc, int32_t base
                                              TT& T, int32_t* __restrict__ stk,
                                              uint32_t& nvis, uint32_t& ntest, bool skip) {
     if (skip) return;
-    const R ix = inv_(d.x), iy = inv_(d.y), iz = inv_(d.z);
-    const R oix = o.x * ix, oiy = o.y * iy, oiz = o.z * iz;
+    R ix, iy, iz, oix, oiy, oiz;
+    slab_axis(o.x, d.x, ix, oix);
+    slab_axis(o.y, d.y, iy, oiy);
+    slab_axis(o.z, d.z, iz, oiz);
     const BvhNode<R>* __restrict__ nodes = sc.bvh;
     int32_t sp = 0;
     int32_t node = 0;
@@ -220,7 +252,12 @@ __device__ __forceinline__ void bvh_traverse(const DevScene<R>& sc, int32_t base
 // count.  With the default 4-sphere leaves there is exactly one group.
 // f64 leaves: an f32 pre-pass (sphere_may_hit: the light pre-pass of
 // lights_pdf_sum on {c, r^2}, with (r + e)^2 <= r^2 + e (r^2 + 1) + e^2) masks
-// the spheres the ray may hit; only those get the f64 test, each read from
+// the spheres the ray may hit (e >= 2^-19 whatever the scale, so nothing here
+// underflows, and coordinates beyond f32 keep every sphere, see the compares;
+// the direction must keep d . d, its reciprocal and d . (o - c) normal f32
+// numbers: |d|_1 within 2^-60 .. 2^46, the range include/rtw.h states -- below
+// it d . d underflows and tc = +-inf; above it hb can overflow to tc = -inf,
+// l2 = inf while (2^-18 |f|)^2, the bound, is still finite); only those get the f64 test, each read from
 // the f64 leaf array -- the closest (t, id) does not depend on the order or on
 // spheres the ray misses.  The pre-pass reads the leaf spheres rounded to f32
 // (DevScene::bsph32, staged in LDS by the LDS-world kernel: half the bytes of
@@ -238,7 +275,17 @@ __device__ __forceinline__ bool sphere_may_hit(const R4<float>& S, float ox, flo
     const float f2 = __builtin_fmaf(fx, fx, __builtin_fmaf(fy, fy, fz * fz));
     const float e = 0x1p-18f * (on + fabsf(cx) + fabsf(cy) + fabsf(cz) + 0.5f * (r2 + 1.0f));
     const float rr = __builtin_fmaf(e, r2 + 1.0f + e, r2);
-    return (l2 <= rr) & ((hb <= 2.0f * e * dn) | (f2 <= rr));
+    // the compares keep the sphere on a NaN: coordinates beyond f32 (inf - inf)
+    // decide nothing here, the f64 test does (and rejects a NaN ray anyway)
+    return !(l2 > rr) & (!(hb > 2.0f * e * dn) | !(f2 > rr));
+}
+// |o|_1 of the light pre-pass's ray (light_may_hit), not below 2^-32: its slack
+// E >= 2^-18 |o|_1 then stays >= 2^-50, so (r + E)^2 and 2 E |d|_1 are normal
+// f32 numbers however small the scene (a scene of size 2^-70 squares to f32
+// denormals, where the bound on l's error does not hold; there the pre-pass
+// simply keeps more).
+__device__ __forceinline__ float light_on(float ox, float oy, float oz) {
+    return fmaxf(fabsf(ox) + fabsf(oy) + fabsf(oz), 0x1p-32f);
 }
 template <typename R, typename TT>
 __device__ __forceinline__ void test_leaf(const DevScene<R>& sc, int32_t base, int32_t leaf,
@@ -310,10 +357,12 @@ __device__ __forceinline__ void bvh_traverse_ww(const DevScene<R>& sc, int32_t b
                                                 uint32_t& nvis, uint32_t& ntest, bool skip) {
     constexpr int32_t kDone = 0x7fffffff;
     constexpr bool kWide = sizeof(R) == 8;   // f64 ray on the f32 tree: widened intervals
-    const float ix = inv_((float)d.x), iy = inv_((float)d.y), iz = inv_((float)d.z);
-    const float oix = (float)o.x * ix, oiy = (float)o.y * iy, oiz = (float)o.z * iz;
-    // fmaxf drops a NaN (0 x inf: that slab is unbounded anyway); an infinite
-    // o ix (a zero direction component) keeps every box: correct, only slow
+    float ix, iy, iz, oix, oiy, oiz;
+    ray_slabs(mk((float)o.x, (float)o.y, (float)o.z), mk((float)d.x, (float)d.y, (float)d.z), ix, iy, iz, oix,
+                     oiy, oiz);
+    // fmaxf drops a NaN (0 x inf: that slab is unbounded anyway); kWide: an
+    // infinite o ix makes the slack infinite and every widened interval NaN or
+    // [-inf, inf] -- kept by the NaN-keeping compare below (ray_slabs)
     const float slack = kWide ? 0x1p-20f * fmaxf(fmaxf(fabsf(oix), fabsf(oiy)), fmaxf(fabsf(oiz), 0.0f)) : 0.0f;
     float tbw = kWide ? cull_bound(T.bound()) : 0.0f;   // kWide: tb as the culling bound, per leaf phase
     const BvhNode<float>* __restrict__ nodes = cull_nodes(sc);
@@ -351,7 +400,8 @@ __device__ __forceinline__ void bvh_traverse_ww(const DevScene<R>& sc, int32_t b
                         tf[c] = __builtin_fmaf(tf[c], 1.0f + 0x1p-20f, slack);
                     }
                 }
-                const bool h0 = tn[0] <= tf[0], h1 = tn[1] <= tf[1];
+                // (a NaN interval -- kWide, an infinite slack -- keeps the box: ray_slabs)
+                const bool h0 = kWide ? !(tn[0] > tf[0]) : tn[0] <= tf[0], h1 = kWide ? !(tn[1] > tf[1]) : tn[1] <= tf[1];
                 const int32_t c0 = nd.child[0], c1 = nd.child[1];
                 if (h0 && h1) {
                     const bool first0 = tn[0] <= tn[1];
@@ -615,12 +665,8 @@ __device__ __forceinline__ void bvh_traverse_steal(const DevScene<R>& sc, int32_
     int32_t* __restrict__ stk = stk_wave + lane;
     float ix, iy, iz, oix, oiy, oiz, slack, tbw;
     auto setup = [&]() {
-        ix = inv_((float)T.d.x);
-        iy = inv_((float)T.d.y);
-        iz = inv_((float)T.d.z);
-        oix = (float)T.o.x * ix;
-        oiy = (float)T.o.y * iy;
-        oiz = (float)T.o.z * iz;
+        ray_slabs(mk((float)T.o.x, (float)T.o.y, (float)T.o.z), mk((float)T.d.x, (float)T.d.y, (float)T.d.z),
+                         ix, iy, iz, oix, oiy, oiz);
         slack = kWide ? 0x1p-20f * fmaxf(fmaxf(fabsf(oix), fabsf(oiy)), fmaxf(fabsf(oiz), 0.0f)) : 0.0f;
     };
     auto bound = [&]() { tbw = kWide ? cull_bound(T.bound()) : 0.0f; };
@@ -689,7 +735,8 @@ __device__ __forceinline__ void bvh_traverse_steal(const DevScene<R>& sc, int32_
                         tf[c] = __builtin_fmaf(tf[c], 1.0f + 0x1p-20f, slack);
                     }
                 }
-                const bool h0 = tn[0] <= tf[0], h1 = tn[1] <= tf[1];
+                // (a NaN interval -- kWide, an infinite slack -- keeps the box: ray_slabs)
+                const bool h0 = kWide ? !(tn[0] > tf[0]) : tn[0] <= tf[0], h1 = kWide ? !(tn[1] > tf[1]) : tn[1] <= tf[1];
                 const int32_t c0 = nd.child[0], c1 = nd.child[1];
                 if (h0 && h1) {
                     const bool first0 = tn[0] <= tn[1];

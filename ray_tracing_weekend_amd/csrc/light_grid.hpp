@@ -2,7 +2,15 @@
 // query over long light lists, light_pdf.hpp lights_pdf_grid).  Host +
 // device: tests/native/grid_walk_check.cpp runs the f64 instance on the CPU
 // against a brute-force sweep (every hit light counted exactly once), whole
-// and cut into pieces as the wave-cooperative walk cuts it.
+// and cut into pieces as the wave-cooperative walk cuts it.  The f32 instance
+// that the f64 kernels' cooperative walk runs on the grid rounded to f32
+// (lights_pdf_grid_coop64) has no such check of its own: it is only RUN on the
+// GPU by tests/test_gpu_f64_culls.py (scenes whose light queries start 10^4
+// away, or 2^22 from the origin, at 1/16 to 16 cells per light, every pixel
+// the oracle's), and tests/test_gpu_cull_probe.py checks its candidate test
+// (light_may_hit) record by record.  Those renders do not notice a wrong
+// padding bound: with the host's pad term 1e-3 cell set to 0 they all still
+// pass.  A check of the f32 walk against a brute-force sweep is still missing.
 #pragma once
 
 #include <math.h>

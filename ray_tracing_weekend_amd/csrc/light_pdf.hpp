@@ -21,9 +21,14 @@ namespace dev {
 // starts at +0.0), so skipping it changes no bit.  The pre-pass rounds the ray
 // and the light to f32 and tests the closest approach l (see light_hit_f32)
 // against r + E and the direction (hb <= 0 or the origin inside) with slack,
-// E = 2^-18 (|o|_1 + |c|_1 + r): far above the f32 error of l (a few 2^-24
-// (|o| + |c|)) and of the f64 decision itself (disc's rounding), so every
-// light the f64 test hits stays in.
+// E = 2^-18 (max(|o|_1, 2^-32) + |c|_1 + r): far above the f32 error of l (a
+// few 2^-24 (|o| + |c|)) and of the f64 decision itself (disc's rounding), so
+// every light the f64 test hits stays in -- while the f32 values are normal
+// numbers: the floor under |o|_1 (light_on) keeps E^2 normal for tiny scenes,
+// and the compares keep a light on NaN (coordinates beyond f32: inf - inf), so
+// the scene's size is free; the direction must keep d . d, its reciprocal and
+// d . (o - c) normal f32 numbers: |d|_1 within 2^-60 .. 2^46 (include/rtw.h
+// states that range; above it hb can overflow against a finite bound).
 // li32 (may be null): the same lights rounded to f32 with |radius| (staged in
 // LDS by the LDS-world kernels): the pre-pass reads them instead of converting
 // the f64 records -- the same f32 values, the same mask
@@ -36,10 +41,11 @@ __device__ __forceinline__ bool light_may_hit(float cx, float cy, float cz, floa
     const float lx = __builtin_fmaf(tc, dx, fx), ly = __builtin_fmaf(tc, dy, fy), lz = __builtin_fmaf(tc, dz, fz);
     const float l2 = __builtin_fmaf(lx, lx, __builtin_fmaf(ly, ly, lz * lz));
     const float f2 = __builtin_fmaf(fx, fx, __builtin_fmaf(fy, fy, fz * fz));
-    const float e = 0x1p-18f * (on + fabsf(cx) + fabsf(cy) + fabsf(cz) + r);
+    const float e = 0x1p-18f * (on + fabsf(cx) + fabsf(cy) + fabsf(cz) + r);   // on >= 2^-32: light_on
     const float rr = (r + e) * (r + e);
-    // NaN anywhere (a NaN ray): no candidate; the f64 test gives 0 too
-    return (l2 <= rr) & ((hb <= 2.0f * e * dn) | (f2 <= rr));
+    // the compares keep the light on a NaN: coordinates beyond f32 (inf - inf)
+    // decide nothing here, the f64 test does (a NaN ray's pdf is 0 there too)
+    return !(l2 > rr) & (!(hb > 2.0f * e * dn) | !(f2 > rr));
 }
 // The f32 ray of the pre-pass: o, d rounded, 1 / (d . d), |o|_1, |d|_1
 struct LightPre {
@@ -47,7 +53,7 @@ struct LightPre {
     __device__ __forceinline__ LightPre(V3<double> o, V3<double> d)
         : ox((float)o.x), oy((float)o.y), oz((float)o.z), dx((float)d.x), dy((float)d.y), dz((float)d.z) {
         ia = __builtin_amdgcn_rcpf(__builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, dz * dz)));
-        on = fabsf(ox) + fabsf(oy) + fabsf(oz);
+        on = light_on(ox, oy, oz);
         dn = fabsf(dx) + fabsf(dy) + fabsf(dz);
     }
     __device__ __forceinline__ bool may_hit(const R4<double>& L) const {
@@ -114,7 +120,7 @@ __device__ __forceinline__ double lights_pdf_sum(const R4<double>* __restrict__ 
     const float dx = (float)d.x, dy = (float)d.y, dz = (float)d.z;
     const float a = __builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, dz * dz));
     const float ia = __builtin_amdgcn_rcpf(a);
-    const float on = fabsf(ox) + fabsf(oy) + fabsf(oz);
+    const float on = light_on(ox, oy, oz);
     const float dn = fabsf(dx) + fabsf(dy) + fabsf(dz);
     double acc = 0.0;
     for (uint32_t base = 0; base < n; base += 32) {
@@ -303,8 +309,10 @@ __device__ __forceinline__ void light_work_wave(unsigned long long* w, LightWork
 template <typename R, typename Leaf>
 __device__ __forceinline__ void light_bvh_walk(const DevScene<R>& sc, V3<R> o, V3<R> d,
                                                int32_t* __restrict__ stk, Leaf&& leaf) {
-    const R ix = inv_(d.x), iy = inv_(d.y), iz = inv_(d.z);
-    const R oix = o.x * ix, oiy = o.y * iy, oiz = o.z * iz;
+    R ix, iy, iz, oix, oiy, oiz;
+    slab_axis(o.x, d.x, ix, oix);
+    slab_axis(o.y, d.y, iy, oiy);
+    slab_axis(o.z, d.z, iz, oiz);
     int32_t sp = 0;
     int32_t node = 0;
     for (;;) {
@@ -666,7 +674,7 @@ __device__ __forceinline__ R lights_pdf_grid_coop_list(const DevScene<float>& g,
                     const float step = (rtf - rtn) / (float)rk;
                     auto t_at = [&](uint32_t q) { return q == 0 ? rtn : __builtin_fmaf((float)q, step, rtn); };
                     // the owner's test quantities, from the same f32 ray
-                    const float ron = fabsf(ro.x) + fabsf(ro.y) + fabsf(ro.z), rdn = fabsf(rd.x) + fabsf(rd.y) + fabsf(rd.z);
+                    const float ron = light_on(ro.x, ro.y, ro.z), rdn = fabsf(rd.x) + fabsf(rd.y) + fabsf(rd.z);
                     const float ra = len2_f32(rd);
                     uint32_t* ent = slots + (gi - B) * kSlot + 1;
                     uint32_t cnt = 0;
@@ -875,7 +883,7 @@ __device__ __forceinline__ double lights_pdf_grid_coop64(const Grid64& sc, bool 
     };
     auto big_hit = [&](const R4<float>& L) {
         const float ib = __builtin_amdgcn_rcpf(__builtin_fmaf(df.x, df.x, __builtin_fmaf(df.y, df.y, df.z * df.z)));
-        const float on = fabsf(of.x) + fabsf(of.y) + fabsf(of.z), dn = fabsf(df.x) + fabsf(df.y) + fabsf(df.z);
+        const float on = light_on(of.x, of.y, of.z), dn = fabsf(df.x) + fabsf(df.y) + fabsf(df.z);
         return light_may_hit(L.x, L.y, L.z, L.w, of.x, of.y, of.z, df.x, df.y, df.z, ib, on, dn);
     };
     auto pdf_at = [&](uint32_t id, uint32_t owner) {   // the owner's f64 ray from its stash column
