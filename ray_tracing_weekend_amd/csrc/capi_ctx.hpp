@@ -121,7 +121,7 @@ struct rtw_ctx {
     LptCache lpt;
     SplitState split;
     rtw_stats last{};
-    int last_variant = 0;             // render kernel of the last render: launch_render_impl's code
+    int last_variant = 0;             // render kernel of the last render: rtw_kernels.h variant_code
     uint32_t last_n_sph = 0;
     uint32_t last_light_bvh = 0;      // KParams::light_bvh of the last render (0: the linear light loop)
     uint32_t last_n_list = 0;         // ... and its light-list length

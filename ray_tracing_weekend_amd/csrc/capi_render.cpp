@@ -69,19 +69,14 @@ void fill_camera(rtw::KParams<R>& p, const rtw_camera* cam) {
     p.max_depth = cam->max_depth;
 }
 
+// the plan's kernel variant, then the chunk reduction into out; a sample window
+// (accum non-null): the fold onto accum instead (out may be null)
 template <typename R>
-int launch_render(const rtw::KParams<R>& p, const rtw::RenderPlan& pl, R* out, hipStream_t stream, hipEvent_t mid) {
-    if constexpr (std::is_same<R, float>::value) return rtw::launch_render_f32(p, pl.world, pl.launch_lds, out, stream, mid);
-    else return rtw::launch_render_f64(p, pl.world, pl.launch_lds, out, stream, mid);
-}
-
-// a sample window: the render kernel, then the fold onto accum (out may be null)
-template <typename R>
-int launch_window(const rtw::KParams<R>& p, const rtw::RenderPlan& pl, double* accum, uint32_t first, R* out,
-                  hipStream_t stream, hipEvent_t mid) {
+int launch_render(const rtw::KParams<R>& p, const rtw::RenderPlan& pl, R* out, hipStream_t stream, hipEvent_t mid,
+                  double* accum = nullptr, uint32_t first = 0) {
     if constexpr (std::is_same<R, float>::value)
-        return rtw::launch_render_window_f32(p, pl.world, pl.launch_lds, accum, first, out, stream, mid);
-    else return rtw::launch_render_window_f64(p, pl.world, pl.launch_lds, accum, first, out, stream, mid);
+        return rtw::launch_render_f32(p, pl.world, pl.opts, pl.launch_lds, out, stream, mid, accum, first);
+    else return rtw::launch_render_f64(p, pl.world, pl.opts, pl.launch_lds, out, stream, mid, accum, first);
 }
 
 // the device's memory, asked once (plan_chunk / plan_windows budget)
@@ -357,7 +352,7 @@ int render_pass_t(rtw_ctx* c, const rtw_camera* cam_in, uint64_t seed, uint32_t 
         HIP_TRY(c, hipEventRecord(ev[1], stream));
     } else if (pass.accum) {
         if (p.max_depth == 0) p.n_tasks = p.n_chunks = 0;   // every sample is 0: the fold alone
-        lrc = launch_window(p, pl, pass.accum, pass.first, reinterpret_cast<R*>(d_out), stream, ev[1]);
+        lrc = launch_render(p, pl, reinterpret_cast<R*>(d_out), stream, ev[1], pass.accum, pass.first);
     } else if (p.spp == 0 || p.max_depth == 0) {
         // depth == 0: every sample is Colour::default() + res = 0 (camera.rs:470-472)
         HIP_TRY(c, hipMemsetAsync(d_out, 0, need_out, stream));
@@ -366,6 +361,9 @@ int render_pass_t(rtw_ctx* c, const rtw_camera* cam_in, uint64_t seed, uint32_t 
         lrc = launch_render(p, pl, reinterpret_cast<R*>(d_out), stream, ev[1]);
     }
     if (lrc < 0) return fail(c, RTW_E_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
+    // (the launcher reports the instantiation it launched, not what it was asked for)
+    if (lrc && lrc != rtw::variant_code(pl.world, pl.opts))
+        return fail(c, RTW_E_DEVICE, "the launched kernel variant is not the render plan's");
     c->last_variant = lrc;
     if (p.tile_cost) {
         rc = lpt_counted(c, key, stream);

@@ -63,6 +63,14 @@ WindowPlan plan_windows(const RenderKnobs& k, uint32_t spp, uint32_t n_local_til
     return w;
 }
 
+// the scene needs the kernels' quad / cuboid code (kOptPrims): quads, cuboids,
+// a mixed light list or a DiffuseLight (whose emission the kernels without it,
+// the Book-1 family, do not accumulate)
+template <typename R>
+static bool scene_has_prims(const DevScene<R>& sc) {
+    return sc.n_quads || sc.n_boxes || sc.lref || sc.emissive;
+}
+
 template <typename R>
 RenderPlan plan_render(const RenderKnobs& k, const DevScene<R>& sc, const rtw_camera& cam, uint32_t n_local_tiles,
                        uint32_t chunk, const SceneScale& scale) {
@@ -107,15 +115,24 @@ RenderPlan plan_render(const RenderKnobs& k, const DevScene<R>& sc, const rtw_ca
                                                            : 0.0;
         p.robust = k.robust == 2 ? (rel > 1e-3 ? 1u : 0u) : (uint32_t)k.robust;
     }
+    // the light pdf goes through the light BVH (same per-lane stack) for
+    // longer light lists: with a BVH world only
+    const uint32_t light_stack = sc.lbvh_depth + 1;
     p.light_bvh = 0;
+    if (p.accel == RTW_ACCEL_BVH && sc.n_lights >= k.light_bvh_min && sc.n_lquads == 0) {
+        if (sc.lg_on) p.light_bvh = 2;                          // light grid
+        else if (light_stack <= kBvhStack) p.light_bvh = 1;  // light BVH
+    }
+    // f64 hit points: the f32 kernels of sphere + plane scenes
+    p.hit64 = k.hit64 ? 1u : 0u;
+    // The kernel's options (rtw_kernels.h kOpt*): textured kernels carry the
+    // quad / cuboid code; the closest-approach tests and the f64 hit points are
+    // f32's, the latter of the kernels without that code.
+    const bool f32 = sizeof(R) == 4;
+    p.opts = (sc.mat_tex ? dev::kOptTex | dev::kOptPrims : (scene_has_prims(sc) ? dev::kOptPrims : 0)) |
+             (f32 && p.robust ? dev::kOptRobust : 0) | (p.light_bvh ? dev::kOptLightBvh : 0);
+    if (f32 && p.hit64 && !(p.opts & dev::kOptPrims)) p.opts |= dev::kOptHit64;
     if (p.accel == RTW_ACCEL_BVH) {
-        // the light pdf goes through the light BVH (same per-lane stack) for
-        // longer light lists
-        const uint32_t light_stack = sc.lbvh_depth + 1;
-        if (sc.n_lights >= k.light_bvh_min && sc.n_lquads == 0) {
-            if (sc.lg_on) p.light_bvh = 2;                          // light grid
-            else if (light_stack <= kBvhStack) p.light_bvh = 1;  // light BVH
-        }
         // the light grid's cooperative walk parks path state in the stack area
         // (f64: one kCoop64Slot-word slot per piece of the walk -- [count, list
         // indices] -- after the kCoopStash64-word stash: 64 pieces per round)
@@ -128,11 +145,10 @@ RenderPlan plan_render(const RenderKnobs& k, const DevScene<R>& sc, const rtw_ca
         const uint32_t bin_stack = std::max(sc.bvh_depth, min_stack);
         // kWorldBvhLds layout: stacks + stealing area (+ light-work counters) (traversal_lds) | f32 nodes
         // (bvh32) | leaf spheres | ids (padded to 8) | lights | (f32) light pairs | (f64) the lights rounded to f32
-        // wide workgroups (rtw_kernels.h block_waves): the f64 kernel of sphere + plane
+        // wide workgroups (rtw_kernels.h kernel_wide): the f64 kernel of sphere + plane
         // scenes with a linear light list -- 16 waves share one copy, which then also
         // holds the f64 spheres twice, in leaf and in id order (32 B each, 32-B aligned)
-        const bool wide = sizeof(R) == 8 && p.light_bvh == 0 && !sc.mat_tex &&
-                          !(sc.n_quads || sc.n_boxes || sc.lref || sc.emissive);
+        const bool wide = dev::kernel_wide(sizeof(R), kWorldBvhLds, p.opts);
         const uint32_t waves = block_waves(wide);
         const size_t tree_lds = traversal_lds<R>(bin_stack, p.light_bvh != 0, waves) +
                                 (wide ? 32 + 2 * (size_t)sc.n_sph * sizeof(R4<double>) : 0) +
@@ -184,9 +200,16 @@ RenderPlan plan_render(const RenderKnobs& k, const DevScene<R>& sc, const rtw_ca
             return p;
         }
     }
-    // f64 hit points: the f32 kernels of sphere + plane scenes (the launch
-    // routes textured / quad / cuboid scenes to kernels without them)
-    p.hit64 = k.hit64 ? 1u : 0u;
+    // The launch's dynamic LDS: the brute-force world in LDS and the tree in LDS
+    // as sized above; the other BVH worlds hold their traversal stacks + stealing
+    // area; the brute-force world read from global memory holds nothing.
+    if (p.world == kWorldGlobal) p.launch_lds = 0;
+    else if (p.world != kWorldLds && p.world != kWorldBvhLds) p.launch_lds = traversal_lds<R>(p.stack, p.light_bvh != 0);
+    if (!dev::variant_exists(!f32, p.world, p.opts)) {
+        p.err = RTW_E_UNSUPPORTED;
+        p.err_text = "no render kernel for this scene and tuning";
+        return p;
+    }
     // auto: walks that cross the whole grid in few pieces give the wave little to
     // share, short ones pay each piece's setup: f32, a fourteenth of the grid's
     // widest side, 4..16 cells (at the default 1/2 cell per light: C3, ~16 cells

@@ -1,8 +1,10 @@
 // render_plan.hpp -- what a render launches: the tuning knobs, and the pure
 // decisions that turn them, the staged scene's counts and the camera into the
-// work decomposition, the world kernel and its LDS (plan_chunk / plan_render)
-// and the longest-tiles-first task list (build_task_list).  Host only, no HIP
-// call: the C-ABI allocates, launches and keeps the caches.
+// work decomposition and the kernel variant -- render_kernel<R, world, opts>
+// and its dynamic LDS, decided here and nowhere else (plan_chunk /
+// plan_render; render_launch.hpp only looks the variant up) -- and the
+// longest-tiles-first task list (build_task_list).  Host only, no HIP call:
+// the C-ABI allocates, launches and keeps the caches.
 #pragma once
 
 #include <stddef.h>
@@ -101,10 +103,11 @@ struct RenderPlan {
     uint32_t group = 1, n_groups = 0;   // chunks per wave task, tasks per tile
     uint32_t n_tasks = 0;               // in the plain tile order (a task list has its own count)
     int accel = RTW_ACCEL_BRUTE;        // RTW_ACCEL_AUTO resolved
-    int world = kWorldLds;              // WorldMode
+    int world = kWorldLds;              // WorldMode: the kernel's kWorld
+    int opts = 0;                       // the kernel's kOpt (rtw_kernels.h kOpt* bits; a variant that exists)
     uint32_t bvh_width = 0;
     uint32_t stack = kBvhStack;         // KParams::stack
-    size_t launch_lds = 0;              // dynamic LDS of the launch
+    size_t launch_lds = 0;              // dynamic LDS the kernel is launched with
     uint32_t light_bvh = 0;             // KParams::light_bvh
     uint32_t grid_piece = 0;            // KParams::grid_piece
     uint32_t hit64 = 0;                 // KParams::hit64

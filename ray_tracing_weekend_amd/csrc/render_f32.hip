@@ -5,14 +5,9 @@
 
 namespace rtw {
 
-int launch_render_f32(const KParams<float>& p, int world, size_t lds_bytes, float* out,
-                      hipStream_t stream, hipEvent_t mid) {
-    return launch_render_impl<float>(p, world, lds_bytes, out, stream, mid);
-}
-
-int launch_render_window_f32(const KParams<float>& p, int world, size_t lds_bytes, double* accum,
-                             uint32_t first_sample, float* out, hipStream_t stream, hipEvent_t mid) {
-    return launch_render_impl<float>(p, world, lds_bytes, out, stream, mid, accum, first_sample);
+int launch_render_f32(const KParams<float>& p, int world, int opts, size_t lds_bytes, float* out,
+                      hipStream_t stream, hipEvent_t mid, double* accum, uint32_t first_sample) {
+    return launch_render_impl<float>(p, world, opts, lds_bytes, out, stream, mid, accum, first_sample);
 }
 
 int launch_assemble_f32(const float* ranks, size_t rank_stride, uint32_t nranks, uint32_t W, uint32_t H,

@@ -5,14 +5,9 @@
 
 namespace rtw {
 
-int launch_render_f64(const KParams<double>& p, int world, size_t lds_bytes, double* out,
-                      hipStream_t stream, hipEvent_t mid) {
-    return launch_render_impl<double>(p, world, lds_bytes, out, stream, mid);
-}
-
-int launch_render_window_f64(const KParams<double>& p, int world, size_t lds_bytes, double* accum,
-                             uint32_t first_sample, double* out, hipStream_t stream, hipEvent_t mid) {
-    return launch_render_impl<double>(p, world, lds_bytes, out, stream, mid, accum, first_sample);
+int launch_render_f64(const KParams<double>& p, int world, int opts, size_t lds_bytes, double* out,
+                      hipStream_t stream, hipEvent_t mid, double* accum, uint32_t first_sample) {
+    return launch_render_impl<double>(p, world, opts, lds_bytes, out, stream, mid, accum, first_sample);
 }
 
 int launch_assemble_f64(const double* ranks, size_t rank_stride, uint32_t nranks, uint32_t W, uint32_t H,

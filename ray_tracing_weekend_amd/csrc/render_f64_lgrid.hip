@@ -13,8 +13,8 @@
 
 namespace rtw {
 
-int launch_render_f64_lgrid(const KParams<double>& p, int world, size_t lds_bytes, hipStream_t stream, int kopt) {
-    return launch_lgrid_impl<double>(p, world, lds_bytes, stream, kopt);
+int launch_render_f64_lgrid(const KParams<double>& p, int world, int opts, size_t lds_bytes, hipStream_t stream) {
+    return launch_variant<double, true>(p, world, opts, lds_bytes, stream, std::make_index_sequence<kVariants>());
 }
 
 }  // namespace rtw

@@ -478,21 +478,11 @@ __device__ V3<R> tex_colour(const DevScene<R>& sc, uint32_t tid, R u, R v, V3<R>
 }
 
 
-// kOpt: compile-time options, chosen per launch by the host
-//   kOptRobust   (f32) closest-approach sphere and light tests (far geometry)
-//   kOptLightBvh (BVH kernels) light pdf through the light BVH (long light lists)
-//   kOptTex      textured materials (DevScene::mat_tex): hit UVs + Texture::get_colour
-//   kOptPrims    quads, transformed cuboids and mixed light lists (DevScene::lref); without
-//                it the kernel is spheres + planes only (the Book-1 scenes) and carries none
-//                of that code -- fewer live registers across the segment loop
-//   kOptHit64    (f32 kernels of sphere + plane scenes) f64 ray origin, own-sphere re-hit test,
-//                hit t and hit point (sphere_t_ref64): the reference's self-intersection odds
-enum : int { kOptRobust = 1, kOptLightBvh = 2, kOptTex = 4, kOptPrims = 8, kOptHit64 = 16 };
-// the kernels with wide workgroups (rtw_kernels.h block_waves): f64, tree in
-// LDS, spheres + planes, linear light list
+// (kOpt: the kOpt* bits of rtw_kernels.h, chosen per render by host/render_plan.cpp)
+// the kernels with wide workgroups (rtw_kernels.h kernel_wide)
 template <typename R, int kWorld, int kOpt>
 constexpr bool kernel_wide() {
-    return sizeof(R) == 8 && kWorld == kWorldBvhLds && (kOpt & (kOptLightBvh | kOptPrims | kOptTex)) == 0;
+    return kernel_wide(sizeof(R), kWorld, kOpt);
 }
 template <typename R, int kWorld, int kOpt>
 constexpr uint32_t kernel_waves() { return block_waves(kernel_wide<R, kWorld, kOpt>()); }

@@ -1,6 +1,8 @@
-// rtw_kernels.h -- host-visible description of the device scene layout and the
-// launch entry points of the gfx950 render kernels (render_f32.hip /
-// render_f64.hip).  Included by the C-ABI (capi_ctx.hpp), host/ and the kernels.
+// rtw_kernels.h -- host-visible description of the device scene layout, the
+// render kernel variants (their option bits, which of them exist, which run
+// wide workgroups) and the launch entry points of the gfx950 render kernels
+// (render_f32.hip / render_f64.hip).  Included by the C-ABI (capi_ctx.hpp),
+// host/ and the kernels.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -81,6 +83,44 @@ enum WorldMode : int {
     kWorldBvh4 = 4,     // 4-wide octant BVH, while-while + leaf postponing
     kWorldBvhLds = 5,   // kWorldBvhWW with nodes + leaf spheres staged in LDS
 };
+
+// The render kernels are render_kernel<R, kWorld, kOpt> (render_kernel.hpp).
+// host/render_plan.cpp picks the variant of a render (RenderPlan::world, opts);
+// render_launch.hpp launches it from a table of the variants that exist.
+namespace dev {
+// kOpt: compile-time options
+//   kOptRobust   (f32) closest-approach sphere and light tests (far geometry)
+//   kOptLightBvh (BVH kernels) light pdf through the light BVH / grid (long light lists)
+//   kOptTex      textured materials (DevScene::mat_tex): hit UVs + Texture::get_colour
+//   kOptPrims    quads, transformed cuboids and mixed light lists (DevScene::lref); without
+//                it the kernel is spheres + planes only (the Book-1 scenes) and carries none
+//                of that code -- fewer live registers across the segment loop
+//   kOptHit64    (f32 kernels of sphere + plane scenes) f64 ray origin, own-sphere re-hit test,
+//                hit t and hit point (sphere_t_ref64): the reference's self-intersection odds
+enum : int { kOptRobust = 1, kOptLightBvh = 2, kOptTex = 4, kOptPrims = 8, kOptHit64 = 16 };
+constexpr int kOptAll = 31;
+// The variants the library holds (98).  Textured kernels carry kOptPrims and
+// exist for the brute-force and binary while-while worlds only (their scenes
+// are small); f64 has neither kOptRobust nor kOptHit64, and kOptHit64 goes
+// without kOptPrims; the light BVH / grid needs a BVH world's per-lane stack.
+// (The f64 kernels with kOptLightBvh are those of render_f64_lgrid.hip.)
+constexpr bool variant_exists(bool f64, int world, int opts) {
+    if (world < kWorldGlobal || world > kWorldBvhLds || (opts & ~kOptAll)) return false;
+    if ((opts & kOptTex) && (!(opts & kOptPrims) || world == kWorldBvh || world == kWorldBvh4)) return false;
+    if ((opts & kOptHit64) && (f64 || (opts & kOptPrims))) return false;
+    if ((opts & kOptRobust) && f64) return false;
+    if ((opts & kOptLightBvh) && world < kWorldBvh) return false;
+    return true;
+}
+// the kernels with wide workgroups (block_waves): f64, tree in LDS, spheres +
+// planes, linear light list
+constexpr bool kernel_wide(size_t sizeof_r, int world, int opts) {
+    return sizeof_r == 8 && world == kWorldBvhLds && (opts & (kOptLightBvh | kOptPrims | kOptTex)) == 0;
+}
+}  // namespace dev
+// what a launch reports (launch_render_*): the instantiation it launched
+constexpr int kVariantRan = 1 << 16;
+constexpr int variant_code(int world, int opts) { return kVariantRan | (world << 8) | opts; }
 
 // material kinds (same codes as RTW_LAMBERTIAN.. in include/rtw.h)
 enum : uint32_t { kMatLambertian = 0, kMatMetal = 1, kMatDielectric = 2, kMatInvisible = 3, kMatDiffuseLight = 4 };
@@ -341,22 +381,20 @@ __host__ __device__ inline uint32_t global_tile(const KParams<R>& p, uint32_t lt
 // whose rays skim the sphere field through thousands of nodes per segment.
 constexpr uint32_t kCostPerSegment = 12;
 
-// Host-side launch helpers (defined in render_f32.hip / render_f64.hip).
-// world: a WorldMode; lds_bytes: dynamic LDS of the kWorldLds variant.
-// `mid` (may be null) is recorded on `stream` between the render kernel and
-// the chunk reduction, so the render kernel can be timed on its own.
-int launch_render_f32(const KParams<float>& p, int world, size_t lds_bytes, float* out,
-                      hipStream_t stream, hipEvent_t mid);
-int launch_render_f64(const KParams<double>& p, int world, size_t lds_bytes, double* out,
-                      hipStream_t stream, hipEvent_t mid);
-// A sample window: the render kernel (p.s_base = the window's first sample,
-// p.spp its length), then fold_window_kernel instead of the chunk reduction --
-// onto accum (n_local_tiles * 64 * 3 doubles; read when first_sample > 0) and,
-// when out is non-null, rounded to R into out.  p.n_tasks 0: the fold alone.
-int launch_render_window_f32(const KParams<float>& p, int world, size_t lds_bytes, double* accum,
-                             uint32_t first_sample, float* out, hipStream_t stream, hipEvent_t mid);
-int launch_render_window_f64(const KParams<double>& p, int world, size_t lds_bytes, double* accum,
-                             uint32_t first_sample, double* out, hipStream_t stream, hipEvent_t mid);
+// Host-side launch helpers (defined in render_f32.hip / render_f64.hip): the
+// render kernel <world, opts> of the plan with lds_bytes of dynamic LDS
+// (RenderPlan::world, opts, launch_lds), then the chunk reduction into out.
+// `mid` (may be null) is recorded on `stream` between the two, so the render
+// kernel can be timed on its own.
+// `accum` non-null: a sample window (p.s_base = its first sample, p.spp its
+// length) -- fold_window_kernel instead of the chunk reduction, onto accum
+// (n_local_tiles * 64 * 3 doubles; read when first_sample > 0) and, when out is
+// non-null, rounded to R into out.  p.n_tasks 0: the fold alone.
+// Returns variant_code of the instantiation launched (0: no render kernel), or -1.
+int launch_render_f32(const KParams<float>& p, int world, int opts, size_t lds_bytes, float* out,
+                      hipStream_t stream, hipEvent_t mid, double* accum, uint32_t first_sample);
+int launch_render_f64(const KParams<double>& p, int world, int opts, size_t lds_bytes, double* out,
+                      hipStream_t stream, hipEvent_t mid, double* accum, uint32_t first_sample);
 // The ranks' packed tiles (nranks buffers, rank_stride elements apart) -> the
 // image [H][W][3] (rtw_assemble_tiles).  slot (may be null: the round robin,
 // T itself): global tile T -> lt * nranks + rank of a dealt split.

@@ -13,7 +13,17 @@
 // the same scene and tuning on an MI355X (16 x 16 pixels, 4 spp, depth 5);
 // stack / launch_lds are not visible through the ABI: they are that library's
 // formula evaluated by hand from the staged scenes' counts, which main()
-// pins first.
+// pins first.  opts (the kernel's option bits) are the rules of the launcher
+// the plan's choice replaced, evaluated by hand per case (below); for the scene
+// families of tests/test_gpu_parity.py's variant test they are also what that
+// library reported through rtw_last_kernel.
+//
+// Then a sweep of the tuning keys over the scenes: every plan without an error
+// names a kernel variant that exists (rtw_kernels.h variant_exists).
+//
+// `plan_check variants` only prints the table of variants, one
+// "variant <f32|f64> <world> <opts>" line each (tests/test_capi_host.py holds
+// it against the library's symbols).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -104,7 +114,7 @@ struct Expect {
     const char* name;
     int accel;
     uint32_t bvh_width;
-    int world;
+    int world, opts;
     uint32_t chunk, stack;
     size_t launch_lds;
 };
@@ -143,12 +153,13 @@ template <typename R>
 static void check_plan(const rtw_scene& s, const rtw_camera& cam, const rtw::RenderKnobs& k, const Expect& e) {
     const rtw::RenderPlan p = plan_of<R>(s, cam, k);
     const char* pr = sizeof(R) == 4 ? "f32" : "f64";
-    printf("plan %-16s %s: accel %d width %u world %d chunk %u stack %u lds %zu light_bvh %u\n", e.name, pr, p.accel,
-           p.bvh_width, p.world, p.chunk, p.stack, p.launch_lds, p.light_bvh);
+    printf("plan %-20s %s: accel %d width %u world %d opts %d chunk %u stack %u lds %zu light_bvh %u\n", e.name, pr,
+           p.accel, p.bvh_width, p.world, p.opts, p.chunk, p.stack, p.launch_lds, p.light_bvh);
     CHECK(p.err == RTW_OK, "%s %s: error %d %s", e.name, pr, p.err, p.err_text);
     CHECK(p.accel == e.accel && p.bvh_width == e.bvh_width && p.world == e.world && p.chunk == e.chunk,
           "%s %s: accel %d width %u world %d chunk %u, expected %d %u %d %u", e.name, pr, p.accel, p.bvh_width,
           p.world, p.chunk, e.accel, e.bvh_width, e.world, e.chunk);
+    CHECK(p.opts == e.opts, "%s %s: opts %d, expected %d", e.name, pr, p.opts, e.opts);
     CHECK(p.stack == e.stack && p.launch_lds == e.launch_lds, "%s %s: stack %u lds %zu, expected %u %zu", e.name, pr,
           p.stack, p.launch_lds, e.stack, e.launch_lds);
 }
@@ -160,6 +171,9 @@ static rtw::RenderKnobs knob(const char* key, uint32_t v) {
     else if (s == "bvh_kind") k.bvh_kind = (int)v;
     else if (s == "bvh_lds_max") k.bvh_lds_max = v;
     else if (s == "light_grid") k.light_grid = v;
+    else if (s == "hit64") k.hit64 = v;
+    else if (s == "robust") k.robust = (int)v;
+    else if (s == "accel") k.accel = (int)v;
     else if (s != "") abort();
     return k;
 }
@@ -170,7 +184,52 @@ static rtw_scene cut(rtw_scene s, uint32_t n) {
     return s;
 }
 
-int main() {
+template <typename R>
+static void sweep_plans(const char* name, const rtw_scene& s, const rtw_camera& cam, int* n_plans) {
+    for (uint32_t light_grid : {8u, 0u}) {
+        rtw::RenderKnobs k;
+        k.light_grid = light_grid;
+        const Staged<R> st = stage<R>(s, k);   // (only the light grid's key changes the staging)
+        const uint32_t nt = rtw::tiles_for_rank(cam.image_width, cam.image_height, 0, 1);
+        for (int accel : {RTW_ACCEL_AUTO, RTW_ACCEL_BRUTE, RTW_ACCEL_BVH})
+            for (int bvh_kind : {0, 1, 2, 3})
+                for (uint32_t hit64 : {0u, 1u})
+                    for (int robust : {0, 1, 2})
+                        for (int world_pref : {0, 1})
+                            for (size_t bvh_lds_max : {(size_t)0, (size_t)1}) {
+                                k.accel = accel;
+                                k.bvh_kind = bvh_kind;
+                                k.hit64 = hit64;
+                                k.robust = robust;
+                                k.world_pref = world_pref;
+                                k.bvh_lds_max = bvh_lds_max;
+                                const rtw::RenderPlan p = rtw::plan_render<R>(k, st.ds, cam, nt, 1, st.scale);
+                                if (p.err != RTW_OK) continue;
+                                ++*n_plans;
+                                CHECK(rtw::dev::variant_exists(sizeof(R) == 8, p.world, p.opts),
+                                      "%s %s: accel %d bvh_kind %d hit64 %u robust %d lds %d bvh_lds_max %zu light_grid "
+                                      "%u plans world %d opts %d, which does not exist", name,
+                                      sizeof(R) == 4 ? "f32" : "f64", accel, bvh_kind, hit64, robust, world_pref,
+                                      bvh_lds_max, light_grid, p.world, p.opts);
+                            }
+    }
+}
+
+static int print_variants() {
+    int n = 0;
+    for (int f64 = 0; f64 < 2; ++f64)
+        for (int world = -1; world <= rtw::kWorldBvhLds + 1; ++world)
+            for (int opts = 0; opts < 64; ++opts)
+                if (rtw::dev::variant_exists(f64 != 0, world, opts)) {
+                    printf("variant %s %d %d\n", f64 ? "f64" : "f32", world, opts);
+                    ++n;
+                }
+    printf("%d variants\n", n);
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && !strcmp(argv[1], "variants")) return print_variants();
     check_task_lists();
 
     const auto simple_t = rtw::scenes::simple(0x5EED0001, 11);
@@ -186,6 +245,18 @@ int main() {
     const rtw::FlatScene tex_f = rtw::flatten(std::get<0>(tex_t), std::get<1>(tex_t));
     const rtw_scene tex = tex_f.view();
     const rtw_camera tex_cam = small_camera(std::get<2>(tex_t));
+    const auto box_t = rtw::scenes::cornell_box();
+    const rtw::FlatScene box_f = rtw::flatten(std::get<0>(box_t), std::get<1>(box_t));
+    const rtw_scene box = box_f.view();
+    const rtw_camera box_cam = small_camera(std::get<2>(box_t));
+    // spheres only, one of them a DiffuseLight: no quad, cuboid or mixed light list
+    rtw::HittableList glow_w, glow_l;
+    glow_w.add(rtw::Sphere{{0, 0, -1}, 0.5, rtw::Material::lambertian({0.5, 0.5, 0.5})});
+    glow_w.add(rtw::Sphere{{0, 1.5, -1}, 0.5, rtw::Material::diffuse_light({4, 4, 4})});
+    glow_l.add(rtw::Sphere{{0, 1.5, -1}, 0.5, rtw::Material::diffuse_light({4, 4, 4})});
+    const rtw::FlatScene glow_f = rtw::flatten(glow_w, glow_l);
+    const rtw_scene glow = glow_f.view();
+    const rtw_camera glow_cam = small_camera(rtw::CameraBuilder());
 
     // the staged scenes' counts the hand-evaluated stack / launch_lds rest on
     {
@@ -209,17 +280,42 @@ int main() {
                   a.ds.bvh4_stack == 13 && b.ds.n_nodes == 156 && b.ds.bvh_depth == 9 && b.ds.bvh4_stack == 13,
               "scenes::simple stages differently");
         CHECK(c.ds.lg_on == 1 && d.ds.lg_on == 0 && d.ds.lbvh_depth == 5, "the 64-light scene stages differently");
-        CHECK(e.ds.n_sph == 2 && e.ds.n_lights == 1 && e.ds.bvh_depth == 1 && e.ds.bvh4_stack == 0 &&
-                  e.ds.mat_tex != nullptr, "checkered_spheres stages differently");
+        CHECK(e.ds.n_sph == 2 && e.ds.n_lights == 1 && e.ds.n_nodes == 1 && e.ds.bvh_depth == 1 &&
+                  e.ds.bvh4_stack == 0 && e.ds.mat_tex != nullptr, "checkered_spheres stages differently");
+        const Staged<float> h = stage<float>(box, k);
+        const Staged<float> i = stage<float>(glow, k);
+        printf("facts cornell_box: spheres %u lights %u quads %u boxes %u light quads %u; glow: spheres %u lights %u "
+               "emissive %u\n", h.ds.n_sph, h.ds.n_lights, h.ds.n_quads, h.ds.n_boxes, h.ds.n_lquads, i.ds.n_sph,
+               i.ds.n_lights, i.ds.emissive);
+        CHECK(h.ds.n_sph == 1 && h.ds.n_lights == 1 && h.ds.n_quads == 6 && h.ds.n_boxes == 1 && h.ds.n_lquads == 1 &&
+                  h.ds.lref != nullptr && !h.ds.mat_tex, "cornell_box stages differently");
+        CHECK(i.ds.n_sph == 2 && i.ds.n_lights == 1 && i.ds.emissive == 1 && !i.ds.n_quads && !i.ds.n_boxes &&
+                  !i.ds.lref && !i.ds.mat_tex, "the emissive sphere scene stages differently");
         CHECK(f.ds.n_nodes == 21 && f.ds.bvh_depth == 5 && g.ds.n_nodes == 21 && g.ds.bvh_depth == 5,
               "the 64-sphere scene stages differently");
     }
 
-    // {name, accel, bvh_width, world, chunk | stack, launch_lds}; the hand evaluation, per precision R
+    // {name, accel, bvh_width, world, opts, chunk | stack, launch_lds}; the hand evaluation, per precision R
     // (s4 = sizeof(R4<R>): 16 / 32; steal = 576 / 1344 B per wave; 4 waves per workgroup, f64 `wide` 16):
-    //   brute worlds:      stack kBvhStack = 32, lds = (spheres + lights) * s4
-    //   worlds 2, 3, 4:    lds as the brute worlds; stack = tree depth (9), bvh4_stack + 1 (14), or
-    //                      the light grid walk's 21 (f32) / 42 (f64) words
+    //   opts (1 robust, 2 light BVH / grid, 4 textures, 8 quads / cuboids / emitters, 16 f64 hit points):
+    //     textured scene 4 + 8; else 8 with a quad, cuboid, mixed light list or DiffuseLight;
+    //     f32: + 1 when `robust` (tuning 1, or 2 and (far / smallest radius)^2 * 5.96e-8 > 1e-3, far = the
+    //       larger of the spheres' extent and the camera's distance from the origin:
+    //       simple and its cuts (15 / 0.2)^2 -> 3.4e-4: off; checkered_spheres (40 / 0.1)^2 -> 9.5e-3: on;
+    //       cornell_box (891 / 90)^2, the emissive spheres (2 / 0.5)^2: off);
+    //     + 2 with a light BVH / grid (BVH worlds only); f32: + 16 with tuning hit64 unless 8 is set
+    //   stack: brute worlds kBvhStack = 32; BVH worlds the tree depth (9), bvh4_stack + 1 (14), or
+    //     the light grid walk's 21 (f32) / 42 (f64) words
+    //   launch_lds, the dynamic LDS the launch passes:
+    //     world 0: 0 (nothing staged)
+    //     world 1: (spheres + lights) * s4
+    //     worlds 2, 3, 4: traversal_lds = 4 * (stack * 256 + steal [+ 16 with a light BVH / grid]).  (Before the
+    //       launcher became a table these plans carried world 1's value, which the launcher ignored: it passed
+    //       this one.)
+    //       stack 9:  f32 4 * (2304 + 576) = 11520           f64 4 * (2304 + 1344) = 14592
+    //       stack 14: f32 4 * (3584 + 576) = 16640           f64 4 * (3584 + 1344) = 19712
+    //       stack 1:  f32 4 * (256 + 576) = 3328             f64 4 * (256 + 1344) = 6400
+    //       light grid: f32 4 * (21 * 256 + 576 + 16) = 23872, f64 4 * (42 * 256 + 1344 + 16) = 48448
     //   world 5 (LDS):     waves * (stack * 256 + steal [+ 16 with a light BVH / grid]) [+ 32 + 2 * spheres * 32, wide]
     //                      + nodes * 64 + spheres * 16 + pad8(spheres) * 4 [+ 32, f64] + lights * s4
     //                      + (f32: pad2(lights) * 16; f64: lights * 16)
@@ -230,29 +326,49 @@ int main() {
     //     64 lights, light grid: 45600 > 36 KiB (f32), 71232 > 52 KiB (f64): the tree stays in L1 / L2
     //     64 spheres f32: 4 * (5 * 256 + 576) + 21 * 64 + 1024 + 256 + 304 + 320 = 10672
     //     64 spheres f64: 16 * (1280 + 1344) + 32 + 4096 + 1344 + 1024 + 256 + 32 + 608 + 304 = 49680
+    //     textured (2 spheres, 1 node, 1 light; not wide): f32 3328 + 64 + 32 + 32 + 16 + 32 = 3504
+    //                                                      f64 6400 + 64 + 32 + 32 + 32 + 32 + 16 = 6608
     struct Case {
         const rtw_scene* scene;
         const rtw_camera* cam;
         rtw::RenderKnobs k;
         Expect f32, f64;
     };
-    rtw::RenderKnobs tex_k = knob("bvh_kind", 2);
-    tex_k.accel = RTW_ACCEL_BVH;
-    const rtw_scene s63 = cut(simple, 63), s64 = cut(simple, 64);
     const int BR = RTW_ACCEL_BRUTE, BV = RTW_ACCEL_BVH;
+    auto tex_k = [&](int kind) {
+        rtw::RenderKnobs k = knob("bvh_kind", (uint32_t)kind);
+        k.accel = BV;
+        return k;
+    };
+    const rtw_scene s63 = cut(simple, 63), s64 = cut(simple, 64);
     const Case cases[] = {
-        {&simple, &cam, knob("", 0), {"defaults", BV, 2, 5, 1, 9, 31824}, {"defaults", BV, 2, 5, 1, 9, 110000}},
-        {&simple, &cam, knob("lds", 0), {"lds 0", BV, 2, 5, 1, 9, 31824}, {"lds 0", BV, 2, 5, 1, 9, 110000}},
-        {&s63, &cam, knob("lds", 0), {"63 spheres lds 0", BR, 0, 0, 1, 32, 1312}, {"63 spheres lds 0", BR, 0, 0, 1, 32, 2624}},
-        {&simple, &cam, knob("bvh_kind", 0), {"bvh_kind 0", BV, 2, 2, 1, 9, 8048}, {"bvh_kind 0", BV, 2, 2, 1, 9, 16096}},
-        {&simple, &cam, knob("bvh_kind", 1), {"bvh_kind 1", BV, 2, 3, 1, 9, 8048}, {"bvh_kind 1", BV, 2, 3, 1, 9, 16096}},
-        {&simple, &cam, knob("bvh_kind", 2), {"bvh_kind 2", BV, 4, 4, 1, 14, 8048}, {"bvh_kind 2", BV, 4, 4, 1, 14, 16096}},
-        {&simple, &cam, knob("bvh_lds_max", 1), {"bvh_lds_max 1", BV, 2, 3, 1, 9, 8048}, {"bvh_lds_max 1", BV, 2, 3, 1, 9, 16096}},
-        {&lights64, &cam, knob("light_grid", 8), {"64 lights grid 8", BV, 2, 3, 1, 21, 8768}, {"64 lights grid 8", BV, 2, 3, 1, 42, 17536}},
-        {&lights64, &cam, knob("light_grid", 0), {"64 lights grid 0", BV, 2, 5, 1, 9, 33312}, {"64 lights grid 0", BV, 2, 5, 1, 9, 37440}},
-        {&tex, &tex_cam, tex_k, {"textured kind 2", BV, 2, 3, 1, 1, 48}, {"textured kind 2", BV, 2, 3, 1, 1, 96}},
-        {&s63, &cam, knob("", 0), {"63 spheres", BR, 0, 1, 1, 32, 1312}, {"63 spheres", BR, 0, 1, 1, 32, 2624}},
-        {&s64, &cam, knob("", 0), {"64 spheres", BV, 2, 5, 1, 5, 10672}, {"64 spheres", BV, 2, 5, 1, 5, 49680}},
+        {&simple, &cam, knob("", 0), {"defaults", BV, 2, 5, 16, 1, 9, 31824}, {"defaults", BV, 2, 5, 0, 1, 9, 110000}},
+        {&simple, &cam, knob("lds", 0), {"lds 0", BV, 2, 5, 16, 1, 9, 31824}, {"lds 0", BV, 2, 5, 0, 1, 9, 110000}},
+        {&s63, &cam, knob("lds", 0), {"63 spheres lds 0", BR, 0, 0, 16, 1, 32, 0}, {"63 spheres lds 0", BR, 0, 0, 0, 1, 32, 0}},
+        {&simple, &cam, knob("bvh_kind", 0), {"bvh_kind 0", BV, 2, 2, 16, 1, 9, 11520}, {"bvh_kind 0", BV, 2, 2, 0, 1, 9, 14592}},
+        {&simple, &cam, knob("bvh_kind", 1), {"bvh_kind 1", BV, 2, 3, 16, 1, 9, 11520}, {"bvh_kind 1", BV, 2, 3, 0, 1, 9, 14592}},
+        {&simple, &cam, knob("bvh_kind", 2), {"bvh_kind 2", BV, 4, 4, 16, 1, 14, 16640}, {"bvh_kind 2", BV, 4, 4, 0, 1, 14, 19712}},
+        {&simple, &cam, knob("bvh_lds_max", 1), {"bvh_lds_max 1", BV, 2, 3, 16, 1, 9, 11520}, {"bvh_lds_max 1", BV, 2, 3, 0, 1, 9, 14592}},
+        {&lights64, &cam, knob("light_grid", 8), {"64 lights grid 8", BV, 2, 3, 18, 1, 21, 23872}, {"64 lights grid 8", BV, 2, 3, 2, 1, 42, 48448}},
+        {&lights64, &cam, knob("light_grid", 0), {"64 lights grid 0", BV, 2, 5, 18, 1, 9, 33312}, {"64 lights grid 0", BV, 2, 5, 2, 1, 9, 37440}},
+        // forced brute force: no light BVH / grid, world 1 with (484 + 64) * s4
+        {&lights64, &cam, knob("accel", (uint32_t)BR), {"64 lights brute", BR, 0, 1, 16, 1, 32, 8768}, {"64 lights brute", BR, 0, 1, 0, 1, 32, 17536}},
+        // textured: kinds 0 and 2 have no textured kernel and take the while-while world
+        {&tex, &tex_cam, tex_k(0), {"textured kind 0", BV, 2, 3, 13, 1, 1, 3328}, {"textured kind 0", BV, 2, 3, 12, 1, 1, 6400}},
+        {&tex, &tex_cam, tex_k(1), {"textured kind 1", BV, 2, 3, 13, 1, 1, 3328}, {"textured kind 1", BV, 2, 3, 12, 1, 1, 6400}},
+        {&tex, &tex_cam, tex_k(2), {"textured kind 2", BV, 2, 3, 13, 1, 1, 3328}, {"textured kind 2", BV, 2, 3, 12, 1, 1, 6400}},
+        {&tex, &tex_cam, tex_k(3), {"textured kind 3", BV, 2, 5, 13, 1, 1, 3504}, {"textured kind 3", BV, 2, 5, 12, 1, 1, 6608}},
+        {&s63, &cam, knob("", 0), {"63 spheres", BR, 0, 1, 16, 1, 32, 1312}, {"63 spheres", BR, 0, 1, 0, 1, 32, 2624}},
+        {&s64, &cam, knob("", 0), {"64 spheres", BV, 2, 5, 16, 1, 5, 10672}, {"64 spheres", BV, 2, 5, 0, 1, 5, 49680}},
+        // the f32 option bits of a sphere + plane scene
+        {&simple, &cam, knob("hit64", 0), {"hit64 0", BV, 2, 5, 0, 1, 9, 31824}, {"hit64 0", BV, 2, 5, 0, 1, 9, 110000}},
+        {&simple, &cam, knob("hit64", 1), {"hit64 1", BV, 2, 5, 16, 1, 9, 31824}, {"hit64 1", BV, 2, 5, 0, 1, 9, 110000}},
+        {&simple, &cam, knob("robust", 0), {"robust 0", BV, 2, 5, 16, 1, 9, 31824}, {"robust 0", BV, 2, 5, 0, 1, 9, 110000}},
+        {&simple, &cam, knob("robust", 1), {"robust 1", BV, 2, 5, 17, 1, 9, 31824}, {"robust 1", BV, 2, 5, 0, 1, 9, 110000}},
+        // quads and a cuboid (1 sphere, 1 sphere light: brute force in LDS, 2 * s4), and a DiffuseLight
+        // alone (2 spheres, 1 light: 3 * s4): the kernels with the quad / cuboid code, no f64 hit points
+        {&box, &box_cam, knob("", 0), {"cornell_box", BR, 0, 1, 8, 1, 32, 32}, {"cornell_box", BR, 0, 1, 8, 1, 32, 64}},
+        {&glow, &glow_cam, knob("", 0), {"emissive sphere", BR, 0, 1, 8, 1, 32, 48}, {"emissive sphere", BR, 0, 1, 8, 1, 32, 96}},
     };
     for (const Case& c : cases) {
         check_plan<float>(*c.scene, *c.cam, c.k, c.f32);
@@ -273,6 +389,19 @@ int main() {
         for (const rtw::RenderPlan* p : {&pa, &pb})
             CHECK(p->err == RTW_E_UNSUPPORTED && !strcmp(p->err_text, "BVH deeper than the kernel's traversal stack"),
                   "deep BVH: error %d '%s'", p->err, p->err_text);
+    }
+    // every plan names a kernel that exists
+    {
+        int n_plans = 0;
+        const std::tuple<const char*, const rtw_scene*, const rtw_camera*> scenes[] = {
+            {"simple", &simple, &cam},       {"63 spheres", &s63, &cam},     {"64 lights", &lights64, &cam},
+            {"textured", &tex, &tex_cam},    {"cornell_box", &box, &box_cam}, {"emissive sphere", &glow, &glow_cam}};
+        for (const auto& sc : scenes) {
+            sweep_plans<float>(std::get<0>(sc), *std::get<1>(sc), *std::get<2>(sc), &n_plans);
+            sweep_plans<double>(std::get<0>(sc), *std::get<1>(sc), *std::get<2>(sc), &n_plans);
+        }
+        printf("sweep: %d plans\n", n_plans);
+        CHECK(n_plans == 6 * 2 * 2 * 3 * 4 * 2 * 3 * 2 * 2, "sweep: %d plans without an error", n_plans);
     }
     printf("%d wrong\n", g_wrong);
     return g_wrong ? 1 : 0;

@@ -238,6 +238,25 @@ def test_kernel_isa_identity_covers_every_render_kernel_variant():
     assert isa.kernel_isa_sha("_ZN3rtw3dev13no_such_kernelEv") is None
 
 
+def test_variant_table_is_the_library_render_kernels():
+    """rtw_kernels.h variant_exists -- what the render plan may pick and the
+    launcher's table holds -- names exactly the render_kernel instantiations of
+    the built library: each has its symbol in a gfx950 code object, and the
+    library has no other."""
+    import subprocess
+    from ray_tracing_weekend_amd import isa
+    from test_render_plan_host import HIPCC, plan_check_exe
+    if not os.path.exists(HIPCC):
+        pytest.skip("hipcc not available")
+    out = subprocess.run([plan_check_exe(), "variants"], capture_output=True, text=True, timeout=60, check=True).stdout
+    table = {isa.render_kernel_symbol(p, int(w), int(o))
+             for p, w, o in re.findall(r"^variant (f32|f64) (-?\d+) (\d+)$", out, flags=re.M)}
+    built = {k for co in isa.gfx950_code_objects() for k in isa.kernel_bytes(co) if "render_kernel" in k}
+    assert len(table) == 98 and len(built) == 98
+    assert table - built == set(), "variants without a kernel in the library"
+    assert built - table == set(), "kernels the table does not know"
+
+
 def test_device_list_arguments_refused_before_any_hip_call():
     """ABI 9: rtw_create_virtual / rtw_create_mask_ex / rtw_create_devices
     reject bad arguments with RTW_E_INVALID before touching HIP (no GPU

@@ -806,3 +806,51 @@ def test_textured_light_grid_scene_every_bvh_kind(kind):
     mae, exact = _compare_f64(gpu, ref, 4)
     assert mae < F64_MAE_TOL and exact > 0.999
     assert segs == st.segments and lambs == st.lambertian
+
+
+# ---- the kernel variant a render launches (host/render_plan.cpp decides it; the
+# launcher reports the instantiation it launched through rtw_last_kernel)
+
+def _variant_scene(name):
+    if name == "simple":
+        return _scene()
+    if name == "lights64":       # the 64-light cut of simple: its first 64 spheres as the light list
+        soa, b = _scene()
+        soa.lights = np.array(np.asarray(soa.spheres).reshape(-1, 4)[:64], np.float64)
+        soa.light_kinds = None
+        return soa, b
+    return rtw.scenes.named_soa(name)
+
+
+# (scene, accel, tuning) -> (kernel, options) in f32, in f64.  Options: 1 robust,
+# 2 light BVH / grid, 4 textures, 8 quads / cuboids / emitters, 16 f64 hit points
+VARIANTS = [
+    ("simple", rtw.RTW_ACCEL_AUTO, {}, (5, 16), (5, 0)),
+    ("simple", rtw.RTW_ACCEL_AUTO, {"bvh_kind": 1}, (3, 16), (3, 0)),
+    ("simple", rtw.RTW_ACCEL_BRUTE, {}, (1, 16), (1, 0)),
+    ("checkered_spheres", rtw.RTW_ACCEL_AUTO, {}, (1, 13), (1, 12)),   # (its f32 tests take the robust form)
+    ("cornell_box", rtw.RTW_ACCEL_AUTO, {}, (1, 8), (1, 8)),
+    ("lights64", rtw.RTW_ACCEL_AUTO, {"light_bvh_min": 1, "light_grid": 8}, (3, 18), (3, 2)),
+    ("lights64", rtw.RTW_ACCEL_AUTO, {"light_bvh_min": 1, "light_grid": 0}, (5, 18), (5, 2)),
+]
+
+
+@pytest.mark.parametrize("scene,accel,tuning,k32,k64", VARIANTS,
+                         ids=[f"{v[0]}-{v[1]}-{'-'.join(f'{k}{x}' for k, x in v[2].items())}" for v in VARIANTS])
+def test_render_launches_the_stated_kernel_variant(scene, accel, tuning, k32, k64):
+    """Each scene family and the tunings that pick another kernel: the render
+    launches render_kernel<R, kernel, options> as stated here (the values are
+    what the library launched before the choice moved into the render plan),
+    and rtw_stats.kernel is that kernel's world."""
+    soa, b = _variant_scene(scene)
+    cam = b.with_image_width(16).with_image_height(16).with_samples_per_pixel(2).with_max_depth(4).build()
+    for prec, want in ((rtw.RTW_F32, k32), (rtw.RTW_F64, k64)):
+        with rtw.Renderer(device=0, precision=prec) as r:
+            for k, v in tuning.items():
+                r.set_tuning(k, v)
+            r.set_accel(accel)
+            r.set_scene(soa)
+            r.render(cam, 3)
+            got, world = r.last_kernel(), r.stats.kernel
+        print(scene, accel, tuning, "f32" if prec == rtw.RTW_F32 else "f64", "launched", got, "stats.kernel", world)
+        assert got == want and world == want[0], (prec, got, world, want)
