@@ -381,6 +381,45 @@ int rtw_render_window_device(rtw_ctx *ctx, const rtw_camera *cam, uint64_t seed,
 int rtw_render_window(rtw_ctx *ctx, const rtw_camera *cam, uint64_t seed,
                       uint32_t first_sample, uint32_t n_samples,
                       double *sums, rtw_stats *stats);
+
+/* ---- adaptive sampling: converged tiles stop between sample passes -------
+ * Opt-in; no other entry point changes.  Pass 0 renders samples [0,
+ * min_samples) of every 8x8 tile; pass k the next `window` samples (up to
+ * max_samples) of the tiles still active, one sample per item.  The fold keeps,
+ * per pixel and in f64, the three colour sums (the additions of a window
+ * render, in sample order) and S1 = sum Y, S2 = sum Y*Y of the samples'
+ * luminance Y = ((0.2126 r) + (0.7152 g)) + (0.0722 b).  After a pass that
+ * ends at n samples a pixel is settled when S1 or S2 is not finite, or when
+ *     m = S1 / n,  q = S2 / n,  var = fmax(q - m*m, 0),  v = var / (n - 1),
+ *     v <= ((4 * tolerance) * tolerance) * fmax(m, 2^-16)
+ * (every operation a separately rounded f64 operation): the standard error of
+ * the displayed value sqrt(mean) is at most `tolerance`, the mean floored at
+ * one 8-bit level squared.  A tile stops when all its pixels inside the image
+ * are settled, or at max_samples, and never resumes; all pixels of a tile
+ * share its count.  So sums[pixel] is the sequential f64 fold of the pixel's
+ * first counts[pixel] samples: rtw_render_window(first 0, n = counts) at
+ * chunk 1, bit for bit.  Stopping on the samples' own variance biases the
+ * estimate slightly (pixels whose first samples happen to agree stop early).
+ * sums: H*W*3 doubles, j = 0 the bottom row; counts: H*W.  cam->
+ * samples_per_pixel and the tuning key "window" are not read.  RTW_E_INVALID
+ * (nothing launched): a NULL pointer, min_samples < 2, max_samples <
+ * min_samples, window == 0, a negative or non-finite tolerance, an explicit
+ * rtw_set_chunk above 1; RTW_E_UNSUPPORTED on a multi-device context;
+ * RTW_E_NO_SCENE.  An image without pixels renders nothing (stats of no
+ * samples).  Stats cover the whole render: samples = the sum of counts,
+ * the counters summed over the passes, chunk = 1.  Synchronous. */
+int rtw_render_adaptive(rtw_ctx *ctx, const rtw_camera *cam, uint64_t seed,
+                        uint32_t min_samples, uint32_t max_samples, uint32_t window,
+                        double tolerance, double *sums, uint32_t *counts, rtw_stats *stats);
+/* Device form: the image-order sums and counts into device memory of the
+ * context's device (RTW_E_INVALID when a buffer is NULL or too small).  The
+ * work runs on `stream`, but the call synchronises with the host once per
+ * pass: it reads back how many tiles go on.  The buffers are complete in
+ * stream order when it returns. */
+int rtw_render_adaptive_device(rtw_ctx *ctx, const rtw_camera *cam, uint64_t seed,
+                               uint32_t min_samples, uint32_t max_samples, uint32_t window,
+                               double tolerance, double *d_sums, size_t sums_bytes,
+                               uint32_t *d_counts, size_t counts_bytes, void *stream);
 uint32_t rtw_tile_size(void);                        /* tile edge in pixels (8) */
 uint32_t rtw_tiles_for_rank(uint32_t image_width, uint32_t image_height, uint32_t rank,
                             uint32_t nranks);
@@ -492,6 +531,12 @@ int rtw_encode_rgb8_f32(const float *sums, uint32_t width, uint32_t height, uint
                         uint8_t *out_rgb);
 int rtw_write_ppm_f32(const char *path, const float *sums, uint32_t width, uint32_t height,
                       uint32_t spp);
+/* The same arithmetic with each pixel's own sample count (counts: H*W, as
+ * rtw_render_adaptive returns them) in place of spp. */
+int rtw_encode_rgb8_counts(const double *sums, const uint32_t *counts, uint32_t width,
+                           uint32_t height, uint8_t *out_rgb);
+int rtw_write_ppm_counts(const char *path, const double *sums, const uint32_t *counts,
+                         uint32_t width, uint32_t height);
 
 #ifdef __cplusplus
 }

@@ -504,6 +504,17 @@ class Camera:
                 sums = r.render_window(self, seed, first, n, sums)
                 yield first + n, sums
 
+    def render_adaptive(self, world, lights, min_samples: int, max_samples: int, window: int, tolerance: float,
+                        *, seed: int = 0x5EED0001, precision: int = RTW_F64, device: int = 0,
+                        accel: int = RTW_ACCEL_AUTO):
+        """Adaptive sampling of the scene (Renderer.render_adaptive): (sums,
+        counts), each tile stopped between min_samples and max_samples once its
+        pixels are within `tolerance`."""
+        with Renderer(device=device, precision=precision) as r:
+            r.set_accel(accel)
+            r.set_scene(flatten(world, lights))
+            return r.render_adaptive(self, seed, min_samples, max_samples, window, tolerance)
+
 
 class Renderer:
     """An rtw_ctx: a device (or, with `devices`, one rank per listed GPU:
@@ -631,6 +642,43 @@ class Renderer:
                                                   first, n, C.c_void_p(accum_ptr) if accum_ptr else None,
                                                   accum_bytes, C.c_void_p(stream) if stream else None),
                     "rtw_render_window_device")
+
+    def render_adaptive(self, cam: Camera, seed: int, min_samples: int, max_samples: int, window: int,
+                        tolerance: float):
+        """Adaptive sampling (rtw_render_adaptive): every 8x8 tile takes
+        min_samples samples, then `window` more at a time up to max_samples,
+        and stops once the standard error of each of its pixels' displayed
+        value sqrt(mean) is at most `tolerance`.  Returns (sums, counts): the
+        float64 [H, W, 3] sums and the uint32 [H, W] samples each pixel took --
+        sums[j, i] is the window render of its first counts[j, i] samples bit
+        for bit.  Stopping on the samples' own variance biases the estimate
+        slightly; cam.samples_per_pixel is not read.  Display with
+        encode_rgb8(sums, counts) / write_ppm(path, sums, counts)."""
+        H, W = cam.raw.image_height, cam.raw.image_width
+        sums = np.zeros((H, W, 3), np.float64)
+        counts = np.zeros((H, W), np.uint32)
+        self._check(_lib.rtw_render_adaptive(self.ctx, C.byref(cam.raw), C.c_uint64(seed), min_samples,
+                                             max_samples, window, float(tolerance),
+                                             sums.ctypes.data_as(_capi._f64p), counts.ctypes.data_as(_capi._u32p),
+                                             C.byref(self.stats)),
+                    "rtw_render_adaptive")
+        return sums, counts
+
+    def render_adaptive_device(self, cam: Camera, seed: int, min_samples: int, max_samples: int, window: int,
+                               tolerance: float, sums_ptr: int, sums_bytes: int, counts_ptr: int,
+                               counts_bytes: int, *, stream: int | None = None):
+        """render_adaptive into device memory (rtw_render_adaptive_device):
+        H*W*3 float64 sums and H*W uint32 counts in image order, on torch's
+        current stream by default.  The call synchronises with the host once
+        per pass (it reads back how many tiles go on)."""
+        if stream is None:
+            stream = _torch_stream(self.device)
+        self._check(_lib.rtw_render_adaptive_device(self.ctx, C.byref(cam.raw), C.c_uint64(seed), min_samples,
+                                                    max_samples, window, float(tolerance),
+                                                    C.c_void_p(sums_ptr) if sums_ptr else None, sums_bytes,
+                                                    C.c_void_p(counts_ptr) if counts_ptr else None, counts_bytes,
+                                                    C.c_void_p(stream) if stream else None),
+                    "rtw_render_adaptive_device")
 
     def render_image_device(self, cam: Camera, seed: int, image_ptr: int, image_bytes: int, *,
                             stream: int | None = None):
@@ -865,22 +913,47 @@ def _sums(sums: np.ndarray):
     return s, s.ctypes.data_as(_capi._f64p), False
 
 
-def encode_rgb8(sums: np.ndarray, spp: int) -> np.ndarray:
+def _counts(spp, H, W):
+    """None for a sample count; for an array of per-pixel counts (an adaptive
+    render's) the contiguous uint32 [H, W] array."""
+    if np.ndim(spp) == 0:
+        return None
+    c = np.ascontiguousarray(spp, np.uint32)
+    if c.shape != (H, W):
+        raise RenderError(_capi.RTW_E_INVALID, f"counts must be [H, W] = [{H}, {W}], got {list(c.shape)}")
+    return c
+
+
+def encode_rgb8(sums: np.ndarray, spp) -> np.ndarray:
     """SampledColour Display (colour.rs:14-36), rows flipped top-first: uint8 [H, W, 3].
-    float32 sums (a speed-mode render) are widened to f64 exactly first."""
+    float32 sums (a speed-mode render) are widened to f64 exactly first.  spp:
+    the sample count, or the [H, W] counts of an adaptive render (each pixel
+    then divides by its own)."""
     s, ptr, f32 = _sums(sums)
     H, W = s.shape[:2]
     out = np.zeros((H, W, 3), np.uint8)
+    c = _counts(spp, H, W)
+    if c is not None:
+        s = np.ascontiguousarray(s, np.float64)
+        _lib.rtw_encode_rgb8_counts(s.ctypes.data_as(_capi._f64p), c.ctypes.data_as(_capi._u32p), W, H,
+                                    out.ctypes.data_as(C.POINTER(C.c_uint8)))
+        return out
     fn = _lib.rtw_encode_rgb8_f32 if f32 else _lib.rtw_encode_rgb8
     fn(ptr, W, H, spp, out.ctypes.data_as(C.POINTER(C.c_uint8)))
     return out
 
 
-def write_ppm(path: str, sums: np.ndarray, spp: int) -> int:
-    """The reference's P3 image.ppm (bin/src/main.rs:89-104)."""
+def write_ppm(path: str, sums: np.ndarray, spp) -> int:
+    """The reference's P3 image.ppm (bin/src/main.rs:89-104); spp as encode_rgb8's."""
     s, ptr, f32 = _sums(sums)
     H, W = s.shape[:2]
-    n = (_lib.rtw_write_ppm_f32 if f32 else _lib.rtw_write_ppm)(path.encode(), ptr, W, H, spp)
+    c = _counts(spp, H, W)
+    if c is not None:
+        s = np.ascontiguousarray(s, np.float64)
+        n = _lib.rtw_write_ppm_counts(path.encode(), s.ctypes.data_as(_capi._f64p), c.ctypes.data_as(_capi._u32p),
+                                      W, H)
+    else:
+        n = (_lib.rtw_write_ppm_f32 if f32 else _lib.rtw_write_ppm)(path.encode(), ptr, W, H, spp)
     if n < 0:
         raise RenderError(n, f"cannot write {path}")
     return n

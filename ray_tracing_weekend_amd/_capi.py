@@ -113,6 +113,11 @@ PROTOTYPES = [
                                            C.c_void_p]),
     ("rtw_render_window", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32, C.c_uint32,
                                     _f64p, C.POINTER(rtw_stats)]),
+    ("rtw_render_adaptive", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32, C.c_uint32,
+                                      C.c_uint32, C.c_double, _f64p, _u32p, C.POINTER(rtw_stats)]),
+    ("rtw_render_adaptive_device", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32,
+                                             C.c_uint32, C.c_uint32, C.c_double, C.c_void_p, C.c_size_t,
+                                             C.c_void_p, C.c_size_t, C.c_void_p]),
     ("rtw_tile_size", C.c_uint32, []),
     ("rtw_tiles_for_rank", C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     ("rtw_assemble_tiles", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
@@ -137,6 +142,8 @@ PROTOTYPES = [
     ("rtw_encode_rgb8_f32", C.c_int, [_f32p, C.c_uint32, C.c_uint32, C.c_uint32,
                                       C.POINTER(C.c_uint8)]),
     ("rtw_write_ppm_f32", C.c_int, [C.c_char_p, _f32p, C.c_uint32, C.c_uint32, C.c_uint32]),
+    ("rtw_encode_rgb8_counts", C.c_int, [_f64p, _u32p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8)]),
+    ("rtw_write_ppm_counts", C.c_int, [C.c_char_p, _f64p, _u32p, C.c_uint32, C.c_uint32]),
 ]
 
 _lib = None

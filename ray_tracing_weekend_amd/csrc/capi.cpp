@@ -45,6 +45,8 @@ void rtw_destroy(rtw_ctx* c) {
     if (c->d_scene) (void)hipFree(c->d_scene);
     if (c->d_partial) (void)hipFree(c->d_partial);
     if (c->d_accum) (void)hipFree(c->d_accum);
+    if (c->d_adapt) (void)hipFree(c->d_adapt);
+    if (c->d_adapt_img) (void)hipFree(c->d_adapt_img);
     if (c->d_out) (void)hipFree(c->d_out);
     if (c->d_img) (void)hipFree(c->d_img);
     if (c->d_counters) (void)hipFree(c->d_counters);

@@ -111,6 +111,13 @@ struct rtw_ctx {
     size_t partial_cap = 0;
     void* d_accum = nullptr;      // sample windows: the f64 running sums of this rank's packed tiles
     size_t accum_cap = 0;
+    // adaptive sampling (capi_render.cpp adaptive_buffers): per global tile the f64 colour
+    // sums and {S1, S2}, the counts and flags, two tile lists and their {length, pixels};
+    // then the image-order sums and counts of the host form
+    void* d_adapt = nullptr;
+    size_t adapt_cap = 0;
+    void* d_adapt_img = nullptr;
+    size_t adapt_img_cap = 0;
     void* d_out = nullptr;        // rtw_render: the packed tiles, then the image
     size_t out_cap = 0;
     void* d_img = nullptr;

@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "capi_ctx.hpp"
+#include "host/render_adaptive.hpp"
 
 namespace {
 
@@ -97,6 +98,13 @@ struct Pass {
     bool begin = true;                // the first pass of a render: counters and stats start here
     const rtw_camera* key_cam = nullptr;   // the camera of the task-order key: the same for every
                                            // window of a render
+    // A pass of an adaptive render (rtw_render_adaptive): the render kernel alone, in tile
+    // order, on the n_tiles global tiles of tile_list (device memory, ascending; null: every
+    // tile of the image) -- the caller folds the chunk sums (c->d_partial, by list position),
+    // and the longest-first cache and the rank split are neither read nor written
+    bool adaptive = false;
+    const uint32_t* tile_list = nullptr;
+    uint32_t n_tiles = 0;
 };
 
 // The tile costs counted by the last counting render (lpt.pending) -> lpt.h_cost
@@ -297,22 +305,22 @@ int render_pass_t(rtw_ctx* c, const rtw_camera* cam_in, uint64_t seed, uint32_t 
     p.rank = rank;
     p.nranks = nranks;
     p.tiles_x = rtw::tiles_across(p.W);
-    p.n_local_tiles = rtw::tiles_for_rank(p.W, p.H, rank, nranks);
+    p.n_local_tiles = pass.adaptive ? pass.n_tiles : rtw::tiles_for_rank(p.W, p.H, rank, nranks);
     const size_t need_out = (size_t)p.n_local_tiles * 64 * 3 * sizeof(R);
-    if (!pass.accum || d_out) {
+    if (!pass.adaptive && (!pass.accum || d_out)) {
         if (out_bytes < need_out) return fail(c, RTW_E_INVALID, "d_out is smaller than tiles_for_rank*64*3");
         if (need_out && !d_out) return fail(c, RTW_E_INVALID, "d_out is NULL");
     }
     // the split's local -> global tile map (a dealt split; null: the round robin)
-    const bool split = c->split.active(p.W, p.H, nranks);
-    p.tile_map = nullptr;
+    const bool split = !pass.adaptive && c->split.active(p.W, p.H, nranks);
+    p.tile_map = pass.adaptive ? pass.tile_list : nullptr;
     if (split && p.n_local_tiles) {
         const int mrc = ensure_tile_map(c, p.W, p.H, rank, nranks);
         if (mrc) return mrc;
         p.tile_map = reinterpret_cast<const uint32_t*>(c->split.d_tile_map);
     }
     rtw::RenderPlan pl;
-    int rc = plan_and_allocate<R>(c, p.sc, cam, p.n_local_tiles, &pl, pass.accum ? pass.chunk : 0u);
+    int rc = plan_and_allocate<R>(c, p.sc, cam, p.n_local_tiles, &pl, pass.accum || pass.adaptive ? pass.chunk : 0u);
     if (rc) return rc;
     p.chunk = pl.chunk;
     p.c_base = p.s_base / std::max(pl.chunk, 1u);
@@ -340,7 +348,7 @@ int render_pass_t(rtw_ctx* c, const rtw_camera* cam_in, uint64_t seed, uint32_t 
         HIP_TRY(c, hipMemsetAsync(c->d_counters + 6, 0, sizeof(unsigned long long), stream));
     }
     const LptKey key = lpt_key(c, pass.key_cam ? pass.key_cam : cam_in, rank, nranks);
-    if (pl.lpt) {
+    if (pl.lpt && !pass.adaptive) {
         rc = lpt_prepare(c, p, pl, key, split, stream);
         if (rc) return rc;
     }
@@ -350,6 +358,11 @@ int render_pass_t(rtw_ctx* c, const rtw_camera* cam_in, uint64_t seed, uint32_t 
     int lrc = 0;
     if (need_out == 0) {
         HIP_TRY(c, hipEventRecord(ev[1], stream));
+    } else if (pass.adaptive) {
+        if (p.max_depth == 0) p.n_tasks = 0;   // every sample is 0: the caller folds no chunk sums
+        if constexpr (std::is_same<R, float>::value)
+            lrc = rtw::launch_render_only_f32(p, pl.world, pl.opts, pl.launch_lds, stream, ev[1]);
+        else lrc = rtw::launch_render_only_f64(p, pl.world, pl.opts, pl.launch_lds, stream, ev[1]);
     } else if (pass.accum) {
         if (p.max_depth == 0) p.n_tasks = p.n_chunks = 0;   // every sample is 0: the fold alone
         lrc = launch_render(p, pl, reinterpret_cast<R*>(d_out), stream, ev[1], pass.accum, pass.first);
@@ -461,6 +474,105 @@ int render_window_t(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t r
     ps.key_cam = &key_cam;
     if (nt == 0) ps.accum = nullptr;   // nothing to fold: the bookkeeping of an empty render
     return render_pass_t<R>(c, cam, seed, rank, nranks, nullptr, 0, stream, ps);
+}
+
+// The adaptive state of an image of nt tiles, carved from c->d_adapt: doubles
+// first (sums nt * 192, s12 nt * 128), then the words.
+struct AdaptiveBuffers {
+    double *sums, *s12;
+    uint32_t *counts, *flags, *list[2], *meta[2];   // meta: {list length, pixels inside the image}
+};
+int adaptive_buffers(rtw_ctx* c, uint32_t nt, AdaptiveBuffers* b) {
+    const size_t doubles = (size_t)nt * 64 * 5, words = (size_t)nt * 4 + 4;
+    const int rc = ensure(c, &c->d_adapt, &c->adapt_cap, doubles * sizeof(double) + words * sizeof(uint32_t));
+    if (rc) return rc;
+    b->sums = reinterpret_cast<double*>(c->d_adapt);
+    b->s12 = b->sums + (size_t)nt * 64 * 3;
+    b->counts = reinterpret_cast<uint32_t*>(b->sums + doubles);
+    b->flags = b->counts + nt;
+    b->list[0] = b->flags + nt;
+    b->list[1] = b->list[0] + nt;
+    b->meta[0] = b->list[1] + nt;
+    b->meta[1] = b->meta[0] + 2;
+    return RTW_OK;
+}
+
+// rtw_render_adaptive_device, its arguments checked: the passes of
+// host/render_adaptive.hpp on render_pass_t's machinery.  Per pass: the render
+// kernel on the active tiles (sub-passes under the chunk-sum budget), the fold
+// with the stop vote, the compaction of the tiles that go on, and one 8-byte
+// read-back with a stream synchronisation -- the next pass is planned for that
+// many tiles.  The passes run in tile order (no task table): the longest-first
+// cache and the split are left as they are.
+template <typename R>
+int render_adaptive_t(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t min_samples, uint32_t max_samples,
+                      uint32_t window, double tolerance, double* d_sums, uint32_t* d_counts, hipStream_t stream) {
+    const uint32_t W = cam->image_width, H = cam->image_height;
+    const uint32_t nt = (uint32_t)rtw::n_tiles_of(W, H);
+    AdaptiveBuffers b{};
+    int rc = adaptive_buffers(c, nt, &b);
+    if (rc) return rc;
+    uint32_t n_active = nt, first = 0;
+    uint64_t active_px = (uint64_t)W * H, total = 0;
+    const uint32_t* list = nullptr;   // pass 0: every tile
+    int cur = 0;
+    const uint32_t n_passes = rtw::adaptive_passes(min_samples, max_samples, window);
+    for (uint32_t k = 0; k < n_passes && n_active; ++k) {
+        const uint32_t end = rtw::adaptive_pass_end(min_samples, max_samples, window, k);
+        const bool last = end == max_samples;
+        const uint32_t cap = rtw::adaptive_sub_samples<R>(c->knobs, n_active, device_total(c));
+        for (uint32_t s = first; s < end;) {
+            const uint32_t n = std::min(cap, end - s);
+            Pass ps;
+            ps.first = s;
+            ps.n = n;
+            ps.chunk = 1;
+            ps.begin = s == 0;
+            ps.adaptive = true;
+            ps.tile_list = list;
+            ps.n_tiles = n_active;
+            rc = render_pass_t<R>(c, cam, seed, 0, 1, nullptr, 0, stream, ps);
+            if (rc) return rc;
+            rtw::AdaptiveFold f{};
+            f.partial = c->d_partial;
+            f.n_chunks = cam->max_depth ? n : 0;   // depth 0: every sample is 0
+            f.list = list;
+            f.n_active = n_active;
+            f.sums = b.sums;
+            f.s12 = b.s12;
+            f.first = s;
+            f.W = W;
+            f.H = H;
+            f.n_end = end;
+            f.decide = s + n == end;
+            f.last = last;
+            f.tolerance = tolerance;
+            f.counts = b.counts;
+            f.flags = b.flags;
+            if (rtw::launch_fold_adaptive(sizeof(R) == 8, f, stream))
+                return fail(c, RTW_E_DEVICE, std::string("adaptive fold launch failed: ") + hipGetErrorString(hipGetLastError()));
+            s += n;
+        }
+        total += active_px * (end - first);
+        first = end;
+        if (last) break;
+        cur ^= 1;
+        if (rtw::launch_compact_tiles(b.flags, nt, W, H, b.list[cur], b.meta[cur], stream))
+            return fail(c, RTW_E_DEVICE, std::string("tile compaction launch failed: ") + hipGetErrorString(hipGetLastError()));
+        uint32_t h_meta[2] = {0, 0};
+        HIP_TRY(c, hipMemcpyAsync(h_meta, b.meta[cur], sizeof h_meta, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(c, hipStreamSynchronize(stream));
+        if (h_meta[0] > n_active) return fail(c, RTW_E_DEVICE, "adaptive: the active tile list grew");
+        n_active = h_meta[0];
+        active_px = h_meta[1];
+        list = b.list[cur];
+    }
+    if (rtw::launch_unpack_adaptive(b.sums, b.counts, W, H, d_sums, d_counts, stream))
+        return fail(c, RTW_E_DEVICE, std::string("adaptive unpack launch failed: ") + hipGetErrorString(hipGetLastError()));
+    HIP_TRY(c, hipEventRecord(c->ev1, stream));   // the stats' time covers the last fold too
+    c->last.samples = total;
+    c->last.chunk = 1;
+    return RTW_OK;
 }
 
 }  // namespace
@@ -594,6 +706,64 @@ int rtw_render_window(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t
     each_pixel([&](size_t img, size_t pk) {
         for (int k = 0; k < 3; ++k) sums[img + k] = packed[pk + k];
     });
+    rtw_stats st{};
+    rc = rtw_get_stats(c, &st);
+    if (stats) *stats = st;
+    return rc;
+}
+
+int rtw_render_adaptive_device(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t min_samples,
+                               uint32_t max_samples, uint32_t window, double tolerance, double* d_sums,
+                               size_t sums_bytes, uint32_t* d_counts, size_t counts_bytes, void* stream) {
+    if (!c || !cam) return fail(c, RTW_E_INVALID, "bad argument");
+    if (c->multi) return fail(c, RTW_E_UNSUPPORTED, "adaptive sampling of a multi-device context");
+    if (!c->has_scene) return fail(c, RTW_E_NO_SCENE, "rtw_set_scene was not called");
+    if (const char* why = rtw::adaptive_check(min_samples, max_samples, window, tolerance, c->knobs.chunk))
+        return fail(c, RTW_E_INVALID, why);
+    const uint32_t W = cam->image_width, H = cam->image_height;
+    if (W > 65535 || H > 65535) return fail(c, RTW_E_UNSUPPORTED, "image width or height beyond 65535");
+    const size_t px = (size_t)W * H;
+    if (px == 0) return RTW_OK;
+    if (!d_sums || !d_counts) return fail(c, RTW_E_INVALID, "d_sums or d_counts is NULL");
+    if (sums_bytes < px * 3 * sizeof(double) || counts_bytes < px * sizeof(uint32_t))
+        return fail(c, RTW_E_INVALID, "d_sums is smaller than H*W*3 doubles or d_counts than H*W");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = resolve_stream(c, stream);
+    c->stats_ranks = 1;
+    return c->precision == RTW_F32
+               ? render_adaptive_t<float>(c, cam, seed, min_samples, max_samples, window, tolerance, d_sums, d_counts, s)
+               : render_adaptive_t<double>(c, cam, seed, min_samples, max_samples, window, tolerance, d_sums, d_counts, s);
+}
+
+int rtw_render_adaptive(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t min_samples, uint32_t max_samples,
+                        uint32_t window, double tolerance, double* sums, uint32_t* counts, rtw_stats* stats) {
+    if (!c || !cam || !sums || !counts) return fail(c, RTW_E_INVALID, "bad argument");
+    if (c->multi) return fail(c, RTW_E_UNSUPPORTED, "adaptive sampling of a multi-device context");
+    if (!c->has_scene) return fail(c, RTW_E_NO_SCENE, "rtw_set_scene was not called");
+    if (const char* why = rtw::adaptive_check(min_samples, max_samples, window, tolerance, c->knobs.chunk))
+        return fail(c, RTW_E_INVALID, why);
+    if (cam->image_width > 65535 || cam->image_height > 65535)
+        return fail(c, RTW_E_UNSUPPORTED, "image width or height beyond 65535");
+    const size_t px = (size_t)cam->image_width * cam->image_height;
+    if (px == 0) {   // nothing to render: the stats of no samples
+        if (stats) {
+            *stats = rtw_stats{};
+            stats->chunk = 1;
+        }
+        return RTW_OK;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the image-order sums, then the counts
+    int rc = ensure(c, &c->d_adapt_img, &c->adapt_img_cap, px * (3 * sizeof(double) + sizeof(uint32_t)));
+    if (rc) return rc;
+    double* d_sums = reinterpret_cast<double*>(c->d_adapt_img);
+    uint32_t* d_counts = reinterpret_cast<uint32_t*>(d_sums + px * 3);
+    rc = rtw_render_adaptive_device(c, cam, seed, min_samples, max_samples, window, tolerance, d_sums,
+                                    px * 3 * sizeof(double), d_counts, px * sizeof(uint32_t), nullptr);
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(sums, d_sums, px * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(counts, d_counts, px * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     rtw_stats st{};
     rc = rtw_get_stats(c, &st);
     if (stats) *stats = st;

@@ -707,24 +707,27 @@ namespace {
 // write_colour, colour.rs:14-36: scale = (spp as f64).recip(); sqrt(c * scale),
 // on the f64 value of each sum (an f32 sum is widened exactly first); rows in
 // reverse, main.rs:97-104
+// (counts non-null: each pixel's own sample count in place of spp)
 template <typename S>
-int encode_rgb8(const S* sums, uint32_t W, uint32_t H, uint32_t spp, uint8_t* out) {
+int encode_rgb8(const S* sums, uint32_t W, uint32_t H, uint32_t spp, uint8_t* out, const uint32_t* counts = nullptr) {
     if ((!sums || !out) && W && H) return RTW_E_INVALID;
-    const double scale = 1.0 / (double)(int32_t)spp;
+    double scale = counts ? 0.0 : 1.0 / (double)(int32_t)spp;
     for (uint32_t r = 0; r < H; ++r) {
         const uint32_t j = H - 1 - r;
-        for (uint32_t i = 0; i < W; ++i)
+        for (uint32_t i = 0; i < W; ++i) {
+            if (counts) scale = 1.0 / (double)(int32_t)counts[(size_t)j * W + i];
             for (int k = 0; k < 3; ++k)
                 out[((size_t)r * W + i) * 3 + k] = to_u8(sqrt((double)sums[((size_t)j * W + i) * 3 + k] * scale));
+        }
     }
     return RTW_OK;
 }
 
 template <typename S>
-int write_ppm(const char* path, const S* sums, uint32_t W, uint32_t H, uint32_t spp) {
+int write_ppm(const char* path, const S* sums, uint32_t W, uint32_t H, uint32_t spp, const uint32_t* counts = nullptr) {
     if (!path) return RTW_E_INVALID;
     std::vector<uint8_t> rgb((size_t)W * H * 3);
-    int rc = encode_rgb8(sums, W, H, spp, rgb.data());
+    int rc = encode_rgb8(sums, W, H, spp, rgb.data(), counts);
     if (rc) return rc;
     FILE* f = fopen(path, "wb");
     if (!f) return RTW_E_INVALID;
@@ -749,6 +752,14 @@ int rtw_write_ppm(const char* path, const double* sums, uint32_t W, uint32_t H, 
 }
 int rtw_write_ppm_f32(const char* path, const float* sums, uint32_t W, uint32_t H, uint32_t spp) {
     return write_ppm(path, sums, W, H, spp);
+}
+int rtw_encode_rgb8_counts(const double* sums, const uint32_t* counts, uint32_t W, uint32_t H, uint8_t* out) {
+    if (!counts && W && H) return RTW_E_INVALID;
+    return encode_rgb8(sums, W, H, 0, out, counts);
+}
+int rtw_write_ppm_counts(const char* path, const double* sums, const uint32_t* counts, uint32_t W, uint32_t H) {
+    if (!counts && W && H) return RTW_E_INVALID;
+    return write_ppm(path, sums, W, H, 0, counts);
 }
 
 }  // extern "C"

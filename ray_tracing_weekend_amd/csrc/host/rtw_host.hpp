@@ -239,6 +239,15 @@ class Camera {
         const HittableList& world, const HittableList& lights, uint32_t window,
         const std::function<bool(uint32_t, const std::vector<double>&)>& on_window,
         const RenderOptions& opt = {}) const;
+    // Adaptive sampling (rtw_render_adaptive, include/rtw.h): every 8x8 tile
+    // takes between min_samples and max_samples samples, `window` at a time,
+    // and stops once its pixels' displayed values are within `tolerance`
+    // (standard error).  Each SampledColour carries its pixel's own sample
+    // count; samples_per_pixel is not read.  Defined in host/render_adaptive.cpp.
+    std::vector<std::vector<SampledColour>> render_adaptive(const HittableList& world, const HittableList& lights,
+                                                            uint32_t min_samples, uint32_t max_samples,
+                                                            uint32_t window, double tolerance,
+                                                            const RenderOptions& opt = {}) const;
     const rtw_camera& raw() const { return c_; }
 
    private:

@@ -10,6 +10,11 @@ int launch_render_f32(const KParams<float>& p, int world, int opts, size_t lds_b
     return launch_render_impl<float>(p, world, opts, lds_bytes, out, stream, mid, accum, first_sample);
 }
 
+int launch_render_only_f32(const KParams<float>& p, int world, int opts, size_t lds_bytes, hipStream_t stream,
+                           hipEvent_t mid) {
+    return launch_render_impl<float>(p, world, opts, lds_bytes, nullptr, stream, mid, nullptr, 0, false);
+}
+
 int launch_assemble_f32(const float* ranks, size_t rank_stride, uint32_t nranks, uint32_t W, uint32_t H,
                         const uint32_t* slot, float* img, hipStream_t stream) {
     return launch_assemble_impl<float>(ranks, rank_stride, nranks, W, H, slot, img, stream);

@@ -78,9 +78,11 @@ int launch_render_f64_lgrid(const KParams<double>& p, int world, int opts, size_
 // the variant that ran (launch_one's code; 0: no launch), or -1.
 // `accum` non-null: a sample window -- fold_window_kernel onto accum (read when
 // first_sample > 0; out may then be null) instead of the chunk reduction.
+// `fold` false: the render kernel alone (the caller folds the chunk sums).
 template <typename R>
 inline int launch_render_impl(const KParams<R>& p_in, int world, int opts, size_t lds_bytes, R* out,
-                              hipStream_t stream, hipEvent_t mid, double* accum, uint32_t first_sample) {
+                              hipStream_t stream, hipEvent_t mid, double* accum, uint32_t first_sample,
+                              bool fold = true) {
     int ran = 0;
     if (p_in.n_tasks) {
         // (a window: the render kernel's absolute view; the fold below reads p_in)
@@ -94,6 +96,7 @@ inline int launch_render_impl(const KParams<R>& p_in, int world, int opts, size_
         if (ran < 0 || hipGetLastError() != hipSuccess) return -1;
     }
     if (mid && hipEventRecord(mid, stream) != hipSuccess) return -1;
+    if (!fold) return ran;
     if (p_in.n_local_tiles && accum) {
         hipLaunchKernelGGL((dev::fold_window_kernel<R>), dim3(p_in.n_local_tiles), dim3(64), 0, stream, p_in,
                            accum, first_sample, out);

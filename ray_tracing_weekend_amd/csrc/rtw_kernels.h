@@ -402,5 +402,37 @@ int launch_assemble_f32(const float* ranks, size_t rank_stride, uint32_t nranks,
                         const uint32_t* slot, float* img, hipStream_t stream);
 int launch_assemble_f64(const double* ranks, size_t rank_stride, uint32_t nranks, uint32_t W, uint32_t H,
                         const uint32_t* slot, double* img, hipStream_t stream);
+// The render kernel alone, without a fold after it (adaptive sampling folds the
+// chunk sums itself); otherwise as launch_render_*.
+int launch_render_only_f32(const KParams<float>& p, int world, int opts, size_t lds_bytes, hipStream_t stream,
+                           hipEvent_t mid);
+int launch_render_only_f64(const KParams<double>& p, int world, int opts, size_t lds_bytes, hipStream_t stream,
+                           hipEvent_t mid);
+
+// Adaptive sampling (adaptive.hip; kernels: adaptive_kernels.hpp).  One fold
+// of a (sub-)pass's chunk sums of the n_active tiles of `list`:
+struct AdaptiveFold {
+    const void* partial;              // [n_active][64][n_chunks][3] of the context's precision, one sample per chunk
+    uint32_t n_chunks;
+    const uint32_t* list;             // the active tiles, ascending (null: every tile, a itself)
+    uint32_t n_active;
+    double* sums;                     // [n_tiles][64][3] colour sums, by global tile
+    double* s12;                      // [n_tiles][64][2] {S1, S2} of the luminance
+    uint32_t first;                   // the (sub-)pass's first sample (0: the state starts from 0)
+    uint32_t W, H;
+    uint32_t n_end;                   // a deciding pass: the samples every active pixel then has
+    uint32_t decide, last;            // the decision is taken; ... and every tile stops (max_samples)
+    double tolerance;
+    uint32_t* counts;                 // [n_tiles] samples of each tile
+    uint32_t* flags;                  // [n_tiles] 1: the tile goes on
+};
+// each returns 0, or -1 when the launch failed
+int launch_fold_adaptive(bool f64, const AdaptiveFold& f, hipStream_t stream);
+// flags -> list (ascending), meta[0] = its length, meta[1] = the pixels inside the image it covers
+int launch_compact_tiles(const uint32_t* flags, uint32_t n_tiles, uint32_t W, uint32_t H, uint32_t* list,
+                         uint32_t* meta, hipStream_t stream);
+// the state by tile -> image-order sums [H][W][3] and counts [H][W]
+int launch_unpack_adaptive(const double* sums, const uint32_t* counts, uint32_t W, uint32_t H, double* img,
+                           uint32_t* img_counts, hipStream_t stream);
 
 }  // namespace rtw
