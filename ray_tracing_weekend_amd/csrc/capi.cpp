@@ -1,5 +1,6 @@
 // capi.cpp -- the C-ABI (include/rtw.h): context, tuning, scene upload, the
 // rank split and stats.  The render entry points are in capi_render.cpp,
+// capi_lpt.cpp (task order) and capi_adaptive.cpp (adaptive sampling),
 // multi-device contexts in capi_multi.cpp, the entry points that are pure host
 // code (camera, scene generators, encoding) in host/rtw_host.cpp.
 #include <algorithm>
@@ -21,8 +22,8 @@ rtw_ctx* rtw_create(int device, int precision) {
     c->precision = precision;
     if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&c->d_counters), rtw_ctx::kCounters * sizeof(unsigned long long)) != hipSuccess ||
-        hipMemset(c->d_counters, 0, rtw_ctx::kCounters * sizeof(unsigned long long)) != hipSuccess) {
+        hipMalloc(reinterpret_cast<void**>(&c->d_counters), rtw::kCounters * sizeof(unsigned long long)) != hipSuccess ||
+        hipMemset(c->d_counters, 0, rtw::kCounters * sizeof(unsigned long long)) != hipSuccess) {
         rtw_destroy(c);
         return nullptr;
     }
@@ -99,7 +100,7 @@ int rtw_set_tuning(rtw_ctx* c, const char* key, int64_t value) {
     else if (k == "lpt_pilot_spp") t.lpt_pilot_spp = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 1), 64);
     else if (k == "lpt_pilot_depth") t.lpt_pilot_depth = (uint32_t)std::min<int64_t>(value, 1u << 20);
     else if (k == "light_bvh_min") t.light_bvh_min = (uint32_t)std::min<int64_t>(value, 1u << 30);
-    else if (k == "max_group") { t.max_group = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 1), 4095); c->lpt.tab_valid = false; }
+    else if (k == "max_group") { t.max_group = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 1), 4095); c->lpt.st.tab_valid = false; }
     else if (k == "grid_piece") t.grid_piece = (uint32_t)std::min<int64_t>(value, 1u << 20);
     else if (k == "partial_max") t.partial_max = std::max<size_t>(1 << 20, (size_t)value);
     else if (k == "group") t.group = (uint32_t)value;
@@ -111,9 +112,9 @@ int rtw_set_tuning(rtw_ctx* c, const char* key, int64_t value) {
     else if (k == "auto_accel") t.auto_accel = (int)std::min<int64_t>(value, RTW_ACCEL_BVH);
     else if (k == "balance") t.balance = value ? 1u : 0u;
     else if (k == "cost_time") t.cost_time = value ? 1u : 0u;
-    else if (k == "guide_div") { t.guide_div = (uint32_t)std::min<int64_t>(value, 1 << 24); c->lpt.tab_valid = false; }
-    else if (k == "guide_max") { t.guide_max = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 1), 4095); c->lpt.tab_valid = false; }
-    else if (k == "guide_floor") { t.guide_floor = std::max<uint64_t>(1, (uint64_t)value); c->lpt.tab_valid = false; }
+    else if (k == "guide_div") { t.guide_div = (uint32_t)std::min<int64_t>(value, 1 << 24); c->lpt.st.tab_valid = false; }
+    else if (k == "guide_max") { t.guide_max = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 1), 4095); c->lpt.st.tab_valid = false; }
+    else if (k == "guide_floor") { t.guide_floor = std::max<uint64_t>(1, (uint64_t)value); c->lpt.st.tab_valid = false; }
     else return fail(c, RTW_E_INVALID, "unknown tuning key " + k);
     return RTW_OK;
 }
@@ -284,7 +285,7 @@ int get_stats_one(rtw_ctx* c, rtw_stats* out) {
     if (c->n_renders == 0) return fail(c, RTW_E_INVALID, "no render yet");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipEventSynchronize(c->ev1));
-    unsigned long long h[rtw_ctx::kCounters] = {};
+    unsigned long long h[rtw::kCounters] = {};
     HIP_TRY(c, hipMemcpy(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost));
     float ms = 0.f;
     HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));

@@ -1,6 +1,6 @@
 // capi_ctx.hpp -- private to the C-ABI units (capi.cpp, capi_render.cpp,
-// capi_multi.cpp): the context behind include/rtw.h's rtw_ctx and the helpers
-// they share.
+// capi_lpt.cpp, capi_adaptive.cpp, capi_multi.cpp): the context behind
+// include/rtw.h's rtw_ctx and the helpers they share.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -13,41 +13,24 @@
 #include <vector>
 
 #include "../../include/rtw.h"
+#include "host/lpt_state.hpp"
+#include "host/render_pass.hpp"
 #include "host/render_plan.hpp"
 #include "host/stage_scene.hpp"
 #include "host/tiles.hpp"
 #include "rtw_kernels.h"
 
-// What a set of tile costs was counted for: the task order of the renders of
-// the same key follows them.
-struct LptKey {
-    rtw_camera cam;
-    uint64_t scene_serial;
-    uint32_t rank, nranks, prec;      // prec: sizeof of the precision
-    uint64_t split;                   // SplitState::id (0 = the round robin)
-    bool operator==(const LptKey& o) const {
-        return scene_serial == o.scene_serial && rank == o.rank && nranks == o.nranks && prec == o.prec &&
-               split == o.split && memcmp(&cam, &o.cam, sizeof cam) == 0;
-    }
-};
+using rtw::LptKey;
 
-// longest-tiles-first task list (pilot render, see capi_render.cpp lpt_pilot / render_plan.hpp build_task_list)
+// longest-tiles-first task order: the state (host/lpt_state.hpp) and its device
+// half (capi_lpt.cpp; build_task_list: host/render_plan.hpp)
 struct LptCache {
-    void* d_cost = nullptr;           // pilot: [tile cost | chunk sums | tiles]
+    rtw::LptState st;
+    void* d_cost = nullptr;           // [tile cost]; a pilot: [tile cost | chunk sums | tiles]
     size_t cost_cap = 0;
-    bool valid = false;               // h_cost is the pilot of `key`
-    bool pending = false;             // ... still on the device: counted by the render before (ev)
-    hipEvent_t ev = nullptr;
-    LptKey key{};
-    std::vector<uint32_t> h_cost;
-    void* d_tasks = nullptr;          // the task list of (h_cost, tab_*)
+    hipEvent_t ev = nullptr;          // after the last counting render (st.pending)
+    void* d_tasks = nullptr;          // the task list st.h_tasks
     size_t tasks_cap = 0;
-    bool tab_valid = false;
-    uint32_t tab_chunks = 0, tab_group = 0;
-    uint64_t tab_target = 0;
-    std::vector<uint32_t> h_tasks;
-    // the context holds (or has pending) tile costs of this key
-    bool has(const LptKey& k) const { return (valid || pending) && key == k; }
 };
 
 // Rank split (ABI 10): renders of a W x H image over n ranks give tile T to
@@ -111,7 +94,7 @@ struct rtw_ctx {
     size_t partial_cap = 0;
     void* d_accum = nullptr;      // sample windows: the f64 running sums of this rank's packed tiles
     size_t accum_cap = 0;
-    // adaptive sampling (capi_render.cpp adaptive_buffers): per global tile the f64 colour
+    // adaptive sampling (capi_adaptive.cpp adaptive_buffers): per global tile the f64 colour
     // sums and {S1, S2}, the counts and flags, two tile lists and their {length, pixels};
     // then the image-order sums and counts of the host form
     void* d_adapt = nullptr;
@@ -122,7 +105,6 @@ struct rtw_ctx {
     size_t out_cap = 0;
     void* d_img = nullptr;
     size_t img_cap = 0;
-    static constexpr int kCounters = 9;   // rtw_kernels.h KParams::counters
     unsigned long long* d_counters = nullptr;
     std::vector<unsigned char> h_out;
     LptCache lpt;
@@ -196,6 +178,32 @@ static inline LptKey lpt_key(const rtw_ctx* c, const rtw_camera* cam, uint32_t r
                   c->split.id(cam->image_width, cam->image_height, nranks)};
 }
 
+// f(R{}) for the context's precision R
+template <typename F>
+auto by_precision(const rtw_ctx* c, F&& f) {
+    return c->precision == RTW_F32 ? f(float{}) : f(double{});
+}
+template <typename R>
+const rtw::DevScene<R>& dev_scene(const rtw_ctx* c) {
+    if constexpr (sizeof(R) == 4) return c->sc32;
+    else return c->sc64;
+}
+
+// the kernel holds a lane's pixel as i | j << 16
+static inline int check_image_size(rtw_ctx* c, const rtw_camera* cam) {
+    if (cam->image_width > 65535 || cam->image_height > 65535)
+        return fail(c, RTW_E_UNSUPPORTED, "image width or height beyond 65535");
+    return RTW_OK;
+}
+
+// the end of a blocking entry point: the stats of the render it waited for
+static inline int fetch_stats(rtw_ctx* c, rtw_stats* stats) {
+    rtw_stats st{};
+    const int rc = rtw_get_stats(c, &st);
+    if (stats) *stats = st;
+    return rc;
+}
+
 // multi-device: every rank alike -- f(peer context) on each peer; the first
 // failure is reported on c
 template <typename F>
@@ -212,7 +220,20 @@ int apply_split(rtw_ctx* c, uint32_t W, uint32_t H, uint32_t nranks, const uint3
                 const uint32_t* tile_cost, bool automatic, const rtw_camera* cam);
 // capi.cpp: the stats of the last render of one rank context (rtw_get_stats sums them)
 int get_stats_one(rtw_ctx* c, rtw_stats* out);
-// capi_render.cpp: the tile costs the context counted for (cam, rank, nranks) under
+// capi_render.cpp: the device's memory, asked once (plan_chunk / plan_windows budget)
+size_t device_total(rtw_ctx* c);
+// capi_render.cpp: one pass of a render of this rank's tiles on `stream` (a window pass
+// writes d_out when it is non-null; d_out holds the rank's packed tiles: the caller checked)
+int render_pass(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t rank, uint32_t nranks, void* d_out,
+                hipStream_t stream, const rtw::Pass& pass);
+// capi_lpt.cpp: the task order of a render of `key` (the plan says longest tiles first
+// applies) -- with costs, p.task_table; a render that counts them on the way, p.tile_cost
+template <typename R>
+int lpt_prepare(rtw_ctx* c, rtw::KParams<R>& p, const rtw::RenderPlan& pl, const LptKey& key, bool split_has_costs,
+                hipStream_t stream);
+// capi_lpt.cpp: after the launch of a render that counts (p.tile_cost)
+int lpt_counted(rtw_ctx* c, const LptKey& key, hipStream_t stream);
+// capi_lpt.cpp: the tile costs the context counted for (cam, rank, nranks) under
 // its split, scattered into cost[global tile]; waits for a pending counting render
 int tile_costs_of(rtw_ctx* c, const rtw_camera* cam, uint32_t rank, uint32_t nranks, uint32_t* cost);
 // capi_multi.cpp: rtw_destroy's part for the ranks of a multi-device context

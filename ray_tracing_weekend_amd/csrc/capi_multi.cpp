@@ -229,7 +229,7 @@ int rtw_render_image_device(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, vo
         bool all = true;
         for (uint32_t k = 0; k < n && all; ++k) {
             const rtw_ctx* ck = rtw_device_ctx(c, k);
-            all = ck->lpt.has(lpt_key(ck, cam, k, n));
+            all = ck->lpt.st.has(lpt_key(ck, cam, k, n));
         }
         if (all) {
             std::vector<uint32_t> cost(rtw::n_tiles_of(W, H), 0), owner(cost.size(), 0);

@@ -3,6 +3,7 @@
 // and the deal itself.  Host only, no HIP call.
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include <algorithm>
@@ -23,6 +24,9 @@ inline uint32_t tiles_for_rank(uint32_t W, uint32_t H, uint32_t rank, uint32_t n
     const uint64_t n = n_tiles_of(W, H);
     return rank < n ? (uint32_t)((n - rank + nranks - 1) / nranks) : 0u;
 }
+
+// the bytes of n_tiles packed tiles [tile][64][3] of elements of elem_bytes
+inline size_t packed_bytes(uint32_t n_tiles, size_t elem_bytes) { return (size_t)n_tiles * 64 * 3 * elem_bytes; }
 
 // the global tiles of `rank`, in the order they are packed (increasing T);
 // split_rank null: the round robin

@@ -74,15 +74,11 @@ inline int launch_variant(const KParams<R>& p, int world, int opts, size_t lds_b
 // the f64 light-grid unit's table (render_f64_lgrid.hip)
 int launch_render_f64_lgrid(const KParams<double>& p, int world, int opts, size_t lds_bytes, hipStream_t stream);
 
-// The render kernel <world, opts>, then the chunk reduction into out.  Returns
+// The render kernel <world, opts>, then the fold (rtw_kernels.h Fold).  Returns
 // the variant that ran (launch_one's code; 0: no launch), or -1.
-// `accum` non-null: a sample window -- fold_window_kernel onto accum (read when
-// first_sample > 0; out may then be null) instead of the chunk reduction.
-// `fold` false: the render kernel alone (the caller folds the chunk sums).
 template <typename R>
-inline int launch_render_impl(const KParams<R>& p_in, int world, int opts, size_t lds_bytes, R* out,
-                              hipStream_t stream, hipEvent_t mid, double* accum, uint32_t first_sample,
-                              bool fold = true) {
+inline int launch_render_impl(const KParams<R>& p_in, int world, int opts, size_t lds_bytes, const Fold<R>& fold,
+                              hipStream_t stream, hipEvent_t mid) {
     int ran = 0;
     if (p_in.n_tasks) {
         // (a window: the render kernel's absolute view; the fold below reads p_in)
@@ -96,22 +92,20 @@ inline int launch_render_impl(const KParams<R>& p_in, int world, int opts, size_
         if (ran < 0 || hipGetLastError() != hipSuccess) return -1;
     }
     if (mid && hipEventRecord(mid, stream) != hipSuccess) return -1;
-    if (!fold) return ran;
-    if (p_in.n_local_tiles && accum) {
+    if (fold.kind == kFoldNone || !p_in.n_local_tiles) return ran;
+    if (fold.kind == kFoldWindow)
         hipLaunchKernelGGL((dev::fold_window_kernel<R>), dim3(p_in.n_local_tiles), dim3(64), 0, stream, p_in,
-                           accum, first_sample, out);
-        if (hipGetLastError() != hipSuccess) return -1;
-    } else if (p_in.n_local_tiles) {
+                           fold.accum, fold.first_sample, fold.out);
+    else
         hipLaunchKernelGGL((dev::reduce_chunks_kernel<R>), dim3(p_in.n_local_tiles), dim3(64), 0, stream, p_in,
-                           out);
-        if (hipGetLastError() != hipSuccess) return -1;
-    }
-    return ran;
+                           fold.out);
+    return hipGetLastError() != hipSuccess ? -1 : ran;
 }
 
+// (explicitly instantiated by the unit of each precision)
 template <typename R>
-inline int launch_assemble_impl(const R* ranks, size_t rank_stride, uint32_t nranks, uint32_t W, uint32_t H,
-                                const uint32_t* slot, R* img, hipStream_t stream) {
+int launch_assemble(const R* ranks, size_t rank_stride, uint32_t nranks, uint32_t W, uint32_t H,
+                    const uint32_t* slot, R* img, hipStream_t stream) {
     const uint32_t tiles_x = (W + kTile - 1) / kTile, n_tiles = tiles_x * ((H + kTile - 1) / kTile);
     const uint32_t blocks = (uint32_t)(((uint64_t)n_tiles * 64 + 255) / 256);
     if (blocks) {

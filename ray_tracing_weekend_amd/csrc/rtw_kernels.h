@@ -118,7 +118,7 @@ constexpr bool kernel_wide(size_t sizeof_r, int world, int opts) {
     return sizeof_r == 8 && world == kWorldBvhLds && (opts & (kOptLightBvh | kOptPrims | kOptTex)) == 0;
 }
 }  // namespace dev
-// what a launch reports (launch_render_*): the instantiation it launched
+// what a launch reports (launch_render): the instantiation it launched
 constexpr int kVariantRan = 1 << 16;
 constexpr int variant_code(int world, int opts) { return kVariantRan | (world << 8) | opts; }
 
@@ -353,6 +353,7 @@ struct KParams {
     // cost per sample -- and is launched with render_kernel_view's copy.
     uint32_t s_base, c_base;
 };
+constexpr int kCounters = 9, kCounterNextTask = 6;   // KParams::counters, host side: how many; [6]
 
 // What the render kernel is launched with: spp and cost_spp as absolute sample
 // bounds, partial moved back by c_base chunks, so that the absolute chunk c of a
@@ -381,33 +382,33 @@ __host__ __device__ inline uint32_t global_tile(const KParams<R>& p, uint32_t lt
 // whose rays skim the sphere field through thousands of nodes per segment.
 constexpr uint32_t kCostPerSegment = 12;
 
+// What follows the render kernel: the chunk reduction into out; a sample window's
+// fold_window_kernel (p.s_base = its first sample, p.spp its length) onto accum
+// (n_local_tiles * 64 * 3 doubles, read when first_sample > 0) and, out non-null,
+// rounded to R into out; or nothing (adaptive sampling folds the chunk sums itself).
+enum FoldKind : int { kFoldReduce, kFoldWindow, kFoldNone };
+template <typename R>
+struct Fold {
+    FoldKind kind;
+    R* out;                           // (window: may be null)
+    double* accum;
+    uint32_t first_sample;            // window: where it starts in the render
+};
 // Host-side launch helpers (defined in render_f32.hip / render_f64.hip): the
-// render kernel <world, opts> of the plan with lds_bytes of dynamic LDS
-// (RenderPlan::world, opts, launch_lds), then the chunk reduction into out.
-// `mid` (may be null) is recorded on `stream` between the two, so the render
-// kernel can be timed on its own.
-// `accum` non-null: a sample window (p.s_base = its first sample, p.spp its
-// length) -- fold_window_kernel instead of the chunk reduction, onto accum
-// (n_local_tiles * 64 * 3 doubles; read when first_sample > 0) and, when out is
-// non-null, rounded to R into out.  p.n_tasks 0: the fold alone.
-// Returns variant_code of the instantiation launched (0: no render kernel), or -1.
-int launch_render_f32(const KParams<float>& p, int world, int opts, size_t lds_bytes, float* out,
-                      hipStream_t stream, hipEvent_t mid, double* accum, uint32_t first_sample);
-int launch_render_f64(const KParams<double>& p, int world, int opts, size_t lds_bytes, double* out,
-                      hipStream_t stream, hipEvent_t mid, double* accum, uint32_t first_sample);
+// render kernel <world, opts> of the plan (RenderPlan::world, opts) with
+// lds_bytes of dynamic LDS (p.n_tasks 0: no kernel), `mid` (may be null)
+// recorded on `stream`, then the fold.  Returns variant_code of the
+// instantiation launched (0: no render kernel), or -1.
+int launch_render(const KParams<float>& p, int world, int opts, size_t lds_bytes, const Fold<float>& fold,
+                  hipStream_t stream, hipEvent_t mid);
+int launch_render(const KParams<double>& p, int world, int opts, size_t lds_bytes, const Fold<double>& fold,
+                  hipStream_t stream, hipEvent_t mid);
 // The ranks' packed tiles (nranks buffers, rank_stride elements apart) -> the
 // image [H][W][3] (rtw_assemble_tiles).  slot (may be null: the round robin,
 // T itself): global tile T -> lt * nranks + rank of a dealt split.
-int launch_assemble_f32(const float* ranks, size_t rank_stride, uint32_t nranks, uint32_t W, uint32_t H,
-                        const uint32_t* slot, float* img, hipStream_t stream);
-int launch_assemble_f64(const double* ranks, size_t rank_stride, uint32_t nranks, uint32_t W, uint32_t H,
-                        const uint32_t* slot, double* img, hipStream_t stream);
-// The render kernel alone, without a fold after it (adaptive sampling folds the
-// chunk sums itself); otherwise as launch_render_*.
-int launch_render_only_f32(const KParams<float>& p, int world, int opts, size_t lds_bytes, hipStream_t stream,
-                           hipEvent_t mid);
-int launch_render_only_f64(const KParams<double>& p, int world, int opts, size_t lds_bytes, hipStream_t stream,
-                           hipEvent_t mid);
+template <typename R>
+int launch_assemble(const R* ranks, size_t rank_stride, uint32_t nranks, uint32_t W, uint32_t H,
+                    const uint32_t* slot, R* img, hipStream_t stream);
 
 // Adaptive sampling (adaptive.hip; kernels: adaptive_kernels.hpp).  One fold
 // of a (sub-)pass's chunk sums of the n_active tiles of `list`:
