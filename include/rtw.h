@@ -370,8 +370,8 @@ int rtw_render_device(rtw_ctx *ctx, const rtw_camera *cam, uint64_t seed,
  * n_samples == 0 does nothing.  RTW_E_INVALID when first_sample + n_samples
  * overflows, first_sample is not a multiple of the chunk (rtw_set_chunk; the
  * auto chunk is 1), d_accum is NULL or accum_bytes too small; RTW_E_UNSUPPORTED
- * on a multi-device context (tuning "window" serves those).  Stats are the
- * window's. */
+ * on a multi-device context (rtw_render_window_image and tuning "window" serve
+ * those).  Stats are the window's. */
 int rtw_render_window_device(rtw_ctx *ctx, const rtw_camera *cam, uint64_t seed,
                              uint32_t rank, uint32_t nranks,
                              uint32_t first_sample, uint32_t n_samples,
@@ -404,8 +404,8 @@ int rtw_render_window(rtw_ctx *ctx, const rtw_camera *cam, uint64_t seed,
  * samples_per_pixel and the tuning key "window" are not read.  RTW_E_INVALID
  * (nothing launched): a NULL pointer, min_samples < 2, max_samples <
  * min_samples, window == 0, a negative or non-finite tolerance, an explicit
- * rtw_set_chunk above 1; RTW_E_UNSUPPORTED on a multi-device context;
- * RTW_E_NO_SCENE.  An image without pixels renders nothing (stats of no
+ * rtw_set_chunk above 1; RTW_E_UNSUPPORTED on a multi-device context
+ * (rtw_render_adaptive_image serves those); RTW_E_NO_SCENE.  An image without pixels renders nothing (stats of no
  * samples).  Stats cover the whole render: samples = the sum of counts,
  * the counters summed over the passes, chunk = 1.  Synchronous. */
 int rtw_render_adaptive(rtw_ctx *ctx, const rtw_camera *cam, uint64_t seed,
@@ -420,6 +420,47 @@ int rtw_render_adaptive_device(rtw_ctx *ctx, const rtw_camera *cam, uint64_t see
                                uint32_t min_samples, uint32_t max_samples, uint32_t window,
                                double tolerance, double *d_sums, size_t sums_bytes,
                                uint32_t *d_counts, size_t counts_bytes, void *stream);
+/* ---- windows and adaptive sampling over every device of the context -------
+ * rtw_render_device is the rank form and rtw_render_image_device the whole
+ * image over all ranks; these are the whole-image forms of the window and
+ * adaptive entry points above.  Semantics, argument checks and error codes are
+ * those of the one-device forms, which keep refusing a multi-device context;
+ * on a one-device context each delegates to its one-device form.  What they
+ * add: on a multi-device context (rtw_create_devices) every rank takes part,
+ * on the tiles the context's split for (W, H, n) gives it (rtw_set_split, a
+ * dealt split, or the round robin: the tiles a fixed render renders there).
+ * Sums, counts and NaN mask equal the one-device entry point's on the same
+ * arguments bit for bit, in both precisions, for any rank count and split
+ * (every (pixel, sample) has its own RNG stream).  Stats are summed over the
+ * ranks as rtw_get_stats sums them: kernel_ms the slowest rank's, samples the
+ * sum of counts (adaptive) or the window's; a rank without a tile contributes
+ * none. */
+/* rtw_render_adaptive over all ranks.  Ownership is static for the render:
+ * each rank runs the passes on its own tiles and compacts its own list, the
+ * ranks take each pass in lockstep (every rank's launch, then every rank's
+ * wait) with no traffic between them; at the end ONE gather brings a record
+ * per tile (its sums and count) to rank 0, which writes the image-order
+ * arrays.  The split is read, never dealt, counted or cleared. */
+int rtw_render_adaptive_image(rtw_ctx *ctx, const rtw_camera *cam, uint64_t seed,
+                              uint32_t min_samples, uint32_t max_samples, uint32_t window,
+                              double tolerance, double *sums, uint32_t *counts, rtw_stats *stats);
+/* rtw_render_adaptive_device over all ranks: d_sums and d_counts are device
+ * memory of the context's first device, complete in `stream`'s order (a stream
+ * of that device: rank 0 renders on it, the gather and the assembly run on it)
+ * when the call returns.  The call synchronises with the host once per pass
+ * and rank. */
+int rtw_render_adaptive_image_device(rtw_ctx *ctx, const rtw_camera *cam, uint64_t seed,
+                                     uint32_t min_samples, uint32_t max_samples, uint32_t window,
+                                     double tolerance, double *d_sums, size_t sums_bytes,
+                                     uint32_t *d_counts, size_t counts_bytes, void *stream);
+/* rtw_render_window over all ranks: each rank continues its tiles of `sums` on
+ * a packed f64 accumulator of its own (f64 whatever the precision), ONE gather,
+ * the f64 assembly on the first device, the download into `sums`.
+ * first_sample must be a multiple of every rank's chunk.  Synchronous.  (No
+ * device-resident form: it would need a scatter of the sums to the ranks.) */
+int rtw_render_window_image(rtw_ctx *ctx, const rtw_camera *cam, uint64_t seed,
+                            uint32_t first_sample, uint32_t n_samples,
+                            double *sums, rtw_stats *stats);
 uint32_t rtw_tile_size(void);                        /* tile edge in pixels (8) */
 uint32_t rtw_tiles_for_rank(uint32_t image_width, uint32_t image_height, uint32_t rank,
                             uint32_t nranks);

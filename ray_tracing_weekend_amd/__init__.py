@@ -486,17 +486,18 @@ class Camera:
     render_debug = render                     # camera.rs:299-312 (no sequential mode on a GPU)
 
     def render_progressive(self, world, lights, window: int, *, seed: int = 0x5EED0001,
-                           precision: int = RTW_F64, device: int = 0):
+                           precision: int = RTW_F64, device: int = 0, devices=None):
         """The render `window` samples at a time: a generator of (samples_done,
         sums) after each window, sums the float64 [H, W, 3] running sums (the
         same array each time: copy it to keep a stage).  The last yield is
         render()'s image bit for bit (at one sample per item, the default).  A
         stage saved with np.savez continues later with
-        Renderer.render_window(cam, seed, samples_done, n, sums)."""
+        Renderer.render_window(cam, seed, samples_done, n, sums).  `devices` as
+        render()'s: every listed GPU renders its tiles of each window."""
         if window < 1:
             raise RenderError(_capi.RTW_E_INVALID, "render_progressive: window must be >= 1")
         spp = self.raw.samples_per_pixel
-        with Renderer(device=device, precision=precision) as r:
+        with Renderer(device=device, precision=precision, devices=devices) as r:
             r.set_scene(flatten(world, lights))
             sums = None
             for first in range(0, spp, window):
@@ -505,12 +506,13 @@ class Camera:
                 yield first + n, sums
 
     def render_adaptive(self, world, lights, min_samples: int, max_samples: int, window: int, tolerance: float,
-                        *, seed: int = 0x5EED0001, precision: int = RTW_F64, device: int = 0,
+                        *, seed: int = 0x5EED0001, precision: int = RTW_F64, device: int = 0, devices=None,
                         accel: int = RTW_ACCEL_AUTO):
         """Adaptive sampling of the scene (Renderer.render_adaptive): (sums,
         counts), each tile stopped between min_samples and max_samples once its
-        pixels are within `tolerance`."""
-        with Renderer(device=device, precision=precision) as r:
+        pixels are within `tolerance`.  `devices` as render()'s: the same sums
+        and counts bit for bit from all the listed GPUs."""
+        with Renderer(device=device, precision=precision, devices=devices) as r:
             r.set_accel(accel)
             r.set_scene(flatten(world, lights))
             return r.render_adaptive(self, seed, min_samples, max_samples, window, tolerance)
@@ -548,10 +550,17 @@ class Renderer:
         self.device = device
         self.precision = precision
         self.stats = _capi.rtw_stats()
+        self._listed = devices is not None or virtual_ranks is not None
 
     @property
     def n_devices(self) -> int:
         return int(_lib.rtw_device_count(self.ctx))
+
+    @property
+    def _whole_image(self) -> bool:
+        """The context is a multi-device one (a list of one GPU included): its
+        window and adaptive renders go through the *_image entry points."""
+        return self.n_devices > 1 or getattr(self, "_listed", False)
 
     def rank_view(self, k: int) -> "_RankView":
         """Rank k's per-device context (stats / timings / last kernel)."""
@@ -617,7 +626,9 @@ class Renderer:
         sums `sums` (float64 [H, W, 3] of samples [0, first); not needed when
         first == 0) in place (rtw_render_window).  Windows folded one after
         another are the one-shot render of as many samples, bit for bit.
-        Returns the sums; cam.samples_per_pixel is not read."""
+        Returns the sums; cam.samples_per_pixel is not read.  On a multi-device
+        Renderer every rank renders its tiles of the window
+        (rtw_render_window_image): the same sums bit for bit."""
         H, W = cam.raw.image_height, cam.raw.image_width
         if sums is None:
             if first:
@@ -625,9 +636,10 @@ class Renderer:
             sums = np.zeros((H, W, 3), np.float64)
         if sums.dtype != np.float64 or sums.shape != (H, W, 3) or not sums.flags.c_contiguous:
             raise RenderError(_capi.RTW_E_INVALID, "sums must be a contiguous float64 array [H, W, 3]")
-        self._check(_lib.rtw_render_window(self.ctx, C.byref(cam.raw), C.c_uint64(seed), first, n,
-                                           sums.ctypes.data_as(_capi._f64p), C.byref(self.stats)),
-                    "rtw_render_window")
+        fn, name = ((_lib.rtw_render_window_image, "rtw_render_window_image") if self._whole_image
+                    else (_lib.rtw_render_window, "rtw_render_window"))
+        self._check(fn(self.ctx, C.byref(cam.raw), C.c_uint64(seed), first, n, sums.ctypes.data_as(_capi._f64p),
+                       C.byref(self.stats)), name)
         return sums
 
     def render_window_device(self, cam: Camera, seed: int, first: int, n: int, accum_ptr: int,
@@ -653,15 +665,17 @@ class Renderer:
         sums[j, i] is the window render of its first counts[j, i] samples bit
         for bit.  Stopping on the samples' own variance biases the estimate
         slightly; cam.samples_per_pixel is not read.  Display with
-        encode_rgb8(sums, counts) / write_ppm(path, sums, counts)."""
+        encode_rgb8(sums, counts) / write_ppm(path, sums, counts).  On a
+        multi-device Renderer every rank runs the passes on the tiles it owns
+        (rtw_render_adaptive_image): the same sums and counts bit for bit."""
         H, W = cam.raw.image_height, cam.raw.image_width
         sums = np.zeros((H, W, 3), np.float64)
         counts = np.zeros((H, W), np.uint32)
-        self._check(_lib.rtw_render_adaptive(self.ctx, C.byref(cam.raw), C.c_uint64(seed), min_samples,
-                                             max_samples, window, float(tolerance),
-                                             sums.ctypes.data_as(_capi._f64p), counts.ctypes.data_as(_capi._u32p),
-                                             C.byref(self.stats)),
-                    "rtw_render_adaptive")
+        fn, name = ((_lib.rtw_render_adaptive_image, "rtw_render_adaptive_image") if self._whole_image
+                    else (_lib.rtw_render_adaptive, "rtw_render_adaptive"))
+        self._check(fn(self.ctx, C.byref(cam.raw), C.c_uint64(seed), min_samples, max_samples, window,
+                       float(tolerance), sums.ctypes.data_as(_capi._f64p), counts.ctypes.data_as(_capi._u32p),
+                       C.byref(self.stats)), name)
         return sums, counts
 
     def render_adaptive_device(self, cam: Camera, seed: int, min_samples: int, max_samples: int, window: int,
@@ -670,15 +684,17 @@ class Renderer:
         """render_adaptive into device memory (rtw_render_adaptive_device):
         H*W*3 float64 sums and H*W uint32 counts in image order, on torch's
         current stream by default.  The call synchronises with the host once
-        per pass (it reads back how many tiles go on)."""
+        per pass (it reads back how many tiles go on).  On a multi-device
+        Renderer (rtw_render_adaptive_image_device) the buffers and the stream
+        are the first device's."""
         if stream is None:
             stream = _torch_stream(self.device)
-        self._check(_lib.rtw_render_adaptive_device(self.ctx, C.byref(cam.raw), C.c_uint64(seed), min_samples,
-                                                    max_samples, window, float(tolerance),
-                                                    C.c_void_p(sums_ptr) if sums_ptr else None, sums_bytes,
-                                                    C.c_void_p(counts_ptr) if counts_ptr else None, counts_bytes,
-                                                    C.c_void_p(stream) if stream else None),
-                    "rtw_render_adaptive_device")
+        fn, name = ((_lib.rtw_render_adaptive_image_device, "rtw_render_adaptive_image_device")
+                    if self._whole_image else (_lib.rtw_render_adaptive_device, "rtw_render_adaptive_device"))
+        self._check(fn(self.ctx, C.byref(cam.raw), C.c_uint64(seed), min_samples, max_samples, window,
+                       float(tolerance), C.c_void_p(sums_ptr) if sums_ptr else None, sums_bytes,
+                       C.c_void_p(counts_ptr) if counts_ptr else None, counts_bytes,
+                       C.c_void_p(stream) if stream else None), name)
 
     def render_image_device(self, cam: Camera, seed: int, image_ptr: int, image_bytes: int, *,
                             stream: int | None = None):

@@ -118,6 +118,13 @@ PROTOTYPES = [
     ("rtw_render_adaptive_device", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32,
                                              C.c_uint32, C.c_uint32, C.c_double, C.c_void_p, C.c_size_t,
                                              C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("rtw_render_adaptive_image", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32, C.c_uint32,
+                                            C.c_uint32, C.c_double, _f64p, _u32p, C.POINTER(rtw_stats)]),
+    ("rtw_render_adaptive_image_device", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32,
+                                                   C.c_uint32, C.c_uint32, C.c_double, C.c_void_p, C.c_size_t,
+                                                   C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("rtw_render_window_image", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32, C.c_uint32,
+                                          _f64p, C.POINTER(rtw_stats)]),
     ("rtw_tile_size", C.c_uint32, []),
     ("rtw_tiles_for_rank", C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     ("rtw_assemble_tiles", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,

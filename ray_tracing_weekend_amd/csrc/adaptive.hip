@@ -30,4 +30,21 @@ int launch_unpack_adaptive(const double* sums, const uint32_t* counts, uint32_t 
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+int launch_pack_adaptive(const uint32_t* tiles, uint32_t n_tiles, const double* sums, const uint32_t* counts,
+                         double* records, hipStream_t stream) {
+    if (n_tiles == 0) return 0;
+    hipLaunchKernelGGL(dev::pack_adaptive_kernel, dim3(n_tiles), dim3(64), 0, stream, tiles, sums, counts, records);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_assemble_adaptive(const double* ranks, size_t rank_stride, uint32_t nranks, uint32_t W, uint32_t H,
+                             const uint32_t* slot, double* img, uint32_t* img_counts, hipStream_t stream) {
+    const uint32_t tiles_x = (W + kTile - 1) / kTile, n_tiles = tiles_x * ((H + kTile - 1) / kTile);
+    const uint32_t blocks = (uint32_t)(((uint64_t)n_tiles * 64 + 255) / 256);
+    if (blocks == 0) return 0;
+    hipLaunchKernelGGL(dev::assemble_adaptive_kernel, dim3(blocks), dim3(256), 0, stream, ranks, rank_stride, nranks,
+                       W, H, tiles_x, n_tiles, slot, img, img_counts);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 }  // namespace rtw

@@ -3,9 +3,11 @@
 // sample passes of the render kernel, fold_adaptive_kernel folds the pass's
 // chunk sums onto each pixel's f64 state and votes per tile,
 // compact_tiles_kernel lists the tiles that go on, and at the end
-// unpack_adaptive_kernel writes the image.  Compiled by adaptive.hip alone,
-// without FMA contraction in either precision: the statistic is f64 arithmetic
-// whose every operation rounds on its own.
+// unpack_adaptive_kernel writes the image -- or, over the ranks of a
+// multi-device context, pack_adaptive_kernel writes each rank's records for the
+// gather and assemble_adaptive_kernel the image on rank 0.  Compiled by
+// adaptive.hip alone, without FMA contraction in either precision: the
+// statistic is f64 arithmetic whose every operation rounds on its own.
 #pragma once
 
 #include "host/render_adaptive.hpp"
@@ -166,6 +168,57 @@ __global__ void __launch_bounds__(256) unpack_adaptive_kernel(const double* __re
     dst[1] = src[1];
     dst[2] = src[2];
     img_counts[(size_t)j * W + i] = counts[T];
+}
+
+// A rank of a multi-device render packs the tiles it owns for the gather: one
+// wave per tile of `tiles` (ascending), each lane its pixel's three sums (24
+// bytes, consecutive lanes consecutive); lane 0 adds the tile's count.  Copies
+// only, no arithmetic.
+__global__ void __launch_bounds__(64) pack_adaptive_kernel(const uint32_t* __restrict__ tiles,
+                                                           const double* __restrict__ sums,
+                                                           const uint32_t* __restrict__ counts,
+                                                           double* __restrict__ records) {
+    const uint32_t lt = blockIdx.x, lane = threadIdx.x;
+    const uint32_t T = tiles[lt];
+    const double* src = sums + ((size_t)T * 64 + lane) * 3;
+    double* rec = records + (size_t)lt * kAdaptiveRecord;
+    double* dst = rec + lane * 3;
+    dst[0] = src[0];
+    dst[1] = src[1];
+    dst[2] = src[2];
+    if (lane == 0) {
+        uint32_t* w = reinterpret_cast<uint32_t*>(rec + 64 * 3);
+        w[0] = counts[T];
+        w[1] = 0;
+    }
+}
+
+// Rank 0 un-interleaves the ranks' gathered records into the image: one thread
+// per pixel slot of every global tile T, decoded as assemble_tiles_kernel
+// decodes it (v = slot[T], or T for the round robin: rank v % nranks, its
+// local tile v / nranks).  Pixels outside the image are never written; every
+// pixel of a tile gets the tile's count.
+__global__ void __launch_bounds__(256) assemble_adaptive_kernel(const double* __restrict__ ranks, size_t rank_stride,
+                                                                uint32_t nranks, uint32_t W, uint32_t H,
+                                                                uint32_t tiles_x, uint32_t n_tiles,
+                                                                const uint32_t* __restrict__ slot,
+                                                                double* __restrict__ img,
+                                                                uint32_t* __restrict__ img_counts) {
+    const uint32_t gid = blockIdx.x * 256 + threadIdx.x;
+    const uint32_t T = gid >> 6, lane = gid & 63;
+    if (T >= n_tiles) return;
+    const uint32_t ty = T / tiles_x, tx = T - ty * tiles_x;
+    const uint32_t i = tx * kTile + (lane & 7), j = ty * kTile + (lane >> 3);
+    if (i >= W || j >= H) return;
+    const uint32_t v = slot ? slot[T] : T;
+    const uint32_t k = v % nranks, lt = v / nranks;
+    const double* rec = ranks + k * rank_stride + (size_t)lt * kAdaptiveRecord;
+    const double* src = rec + lane * 3;
+    double* dst = img + ((size_t)j * W + i) * 3;
+    dst[0] = src[0];
+    dst[1] = src[1];
+    dst[2] = src[2];
+    img_counts[(size_t)j * W + i] = reinterpret_cast<const uint32_t*>(rec + 64 * 3)[0];
 }
 
 }  // namespace dev

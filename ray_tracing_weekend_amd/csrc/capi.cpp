@@ -1,8 +1,9 @@
 // capi.cpp -- the C-ABI (include/rtw.h): context, tuning, scene upload, the
 // rank split and stats.  The render entry points are in capi_render.cpp,
-// capi_lpt.cpp (task order) and capi_adaptive.cpp (adaptive sampling),
-// multi-device contexts in capi_multi.cpp, the entry points that are pure host
-// code (camera, scene generators, encoding) in host/rtw_host.cpp.
+// capi_lpt.cpp (task order) and capi_adaptive.cpp (adaptive sampling, on one
+// device and over the ranks), multi-device contexts in capi_multi.cpp, the
+// entry points that are pure host code (camera, scene generators, encoding) in
+// host/rtw_host.cpp.
 #include <algorithm>
 #include <new>
 #include <type_traits>
@@ -48,6 +49,7 @@ void rtw_destroy(rtw_ctx* c) {
     if (c->d_accum) (void)hipFree(c->d_accum);
     if (c->d_adapt) (void)hipFree(c->d_adapt);
     if (c->d_adapt_img) (void)hipFree(c->d_adapt_img);
+    if (c->h_adapt) (void)hipHostFree(c->h_adapt);
     if (c->d_out) (void)hipFree(c->d_out);
     if (c->d_img) (void)hipFree(c->d_img);
     if (c->d_counters) (void)hipFree(c->d_counters);
@@ -282,6 +284,11 @@ int rtw_get_stats_rank(rtw_ctx* c, uint32_t k, rtw_stats* out) {
 }  // extern "C"
 
 int get_stats_one(rtw_ctx* c, rtw_stats* out) {
+    if (c->no_work) {   // a rank without a tile in the last multi-device render
+        *out = rtw_stats{};
+        out->chunk = 1;
+        return RTW_OK;
+    }
     if (c->n_renders == 0) return fail(c, RTW_E_INVALID, "no render yet");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipEventSynchronize(c->ev1));

@@ -101,6 +101,9 @@ struct rtw_ctx {
     size_t adapt_cap = 0;
     void* d_adapt_img = nullptr;
     size_t adapt_img_cap = 0;
+    // ... and two pinned host words: the {length, pixels} read back after each pass (a
+    // copy into pageable memory could hold the host until the pass is done)
+    uint32_t* h_adapt = nullptr;
     void* d_out = nullptr;        // rtw_render: the packed tiles, then the image
     size_t out_cap = 0;
     void* d_img = nullptr;
@@ -136,6 +139,8 @@ struct rtw_ctx {
     // ranks whose counters the last render filled (rtw_get_stats): n after
     // rtw_render / rtw_render_image_device, 1 after rtw_render_device
     uint32_t stats_ranks = 1;
+    // the last multi-device render gave this rank no tile: its stats are those of no work
+    bool no_work = false;
 };
 
 static inline int fail(rtw_ctx* c, int code, const std::string& msg) {
@@ -236,5 +241,15 @@ int lpt_counted(rtw_ctx* c, const LptKey& key, hipStream_t stream);
 // capi_lpt.cpp: the tile costs the context counted for (cam, rank, nranks) under
 // its split, scattered into cost[global tile]; waits for a pending counting render
 int tile_costs_of(rtw_ctx* c, const rtw_camera* cam, uint32_t rank, uint32_t nranks, uint32_t* cost);
+// capi_render.cpp: the assembly's map of the active split on the device (split.d_tile_slot)
+int ensure_tile_slot(rtw_ctx* c, uint32_t nranks);
+// capi_multi.cpp: ONE gather of the n ranks' packed buffers (`count` elements of
+// elem_bytes -- 4: f32, 8: f64, 1: bytes -- each) to c->d_gather on rank 0, slot k
+// from src[k] on rank k's stream after the work queued there; rank 0 (on s0) filled
+// its slot in place.  RCCL, or on virtual ranks device copies on s0.
+int gather_ranks(rtw_ctx* c, const std::vector<const void*>& src, size_t count, size_t elem_bytes, hipStream_t s0);
+// capi_multi.cpp: after the assembly that read the gathered buffers on s0: every
+// rank's next work waits for it
+int gather_done(rtw_ctx* c, hipStream_t s0);
 // capi_multi.cpp: rtw_destroy's part for the ranks of a multi-device context
 void destroy_ranks(rtw_ctx* c);

@@ -1,6 +1,7 @@
 // capi_multi.cpp -- multi-device contexts of the C-ABI (include/rtw.h): one
-// rank per GPU (or virtual ranks on one), the whole-image render with its
-// gather to rank 0, and the stats summed over the ranks.
+// rank per GPU (or virtual ranks on one), the whole-image render, the gather
+// to rank 0 that it shares with the window and adaptive renders over the ranks
+// (gather_ranks, gather_done), and the stats summed over the ranks.
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -58,6 +59,58 @@ int rccl_fail(rtw_ctx* c, ncclResult_t r, const char* what) {
 }
 
 }  // namespace
+
+int gather_ranks(rtw_ctx* c, const std::vector<const void*>& src, size_t count, size_t elem_bytes, hipStream_t s0) {
+    const uint32_t n = rtw_device_count(c);
+    const size_t bytes = count * elem_bytes;
+    if (c->virt) {
+        // test mode (rtw_create_virtual): the gather as device copies on rank 0's
+        // stream, each after its rank's work -- the same slots an RCCL gather
+        // to root 0 fills
+        for (uint32_t k = 1; k < n; ++k) {
+            rtw_ctx* ck = rtw_device_ctx(c, k);
+            HIP_TRY(c, hipEventRecord(c->peer_ev[k - 1], ck->stream));
+            HIP_TRY(c, hipStreamWaitEvent(s0, c->peer_ev[k - 1], 0));
+            HIP_TRY(c, hipMemcpyAsync(static_cast<unsigned char*>(c->d_gather) + (size_t)k * bytes, src[k], bytes,
+                                      hipMemcpyDeviceToDevice, s0));
+        }
+        return RTW_OK;
+    }
+    // ONE gather of the packed buffers to rank 0 (RCCL over xGMI), ordered after
+    // each rank's work on that rank's stream
+    const RcclApi& api = rccl_api();
+    const ncclDataType_t dt = elem_bytes == 4 ? ncclFloat32 : elem_bytes == 8 ? ncclFloat64 : ncclUint8;
+    const size_t cnt = elem_bytes == 4 || elem_bytes == 8 ? count : bytes;
+    ncclResult_t r = api.group_start();
+    if (r != ncclSuccess) return rccl_fail(c, r, "ncclGroupStart");
+    for (uint32_t k = 0; k < n; ++k) {
+        rtw_ctx* ck = rtw_device_ctx(c, k);
+        r = api.gather(k ? src[k] : c->d_gather, k ? nullptr : c->d_gather, cnt, dt, 0, c->comms[k],
+                       k ? ck->stream : s0);
+        if (r != ncclSuccess) {
+            (void)api.group_end();
+            return rccl_fail(c, r, "ncclGather");
+        }
+    }
+    r = api.group_end();
+    if (r != ncclSuccess) return rccl_fail(c, r, "ncclGroupEnd");
+    return RTW_OK;
+}
+
+int gather_done(rtw_ctx* c, hipStream_t s0) {
+    // every rank's next render waits for this gather + assembly (a peer's
+    // packed buffer is read on s0 in the virtual mode; d_gather always)
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipEventRecord(c->gather_ev, s0));
+    for (uint32_t k = 1; k < rtw_device_count(c); ++k) {
+        rtw_ctx* ck = rtw_device_ctx(c, k);
+        HIP_TRY(c, hipSetDevice(ck->device));
+        HIP_TRY(c, hipStreamWaitEvent(ck->stream, c->gather_ev, 0));
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->gather_pending = true;
+    return RTW_OK;
+}
 
 void destroy_ranks(rtw_ctx* c) {
     if (!c->comms.empty()) {
@@ -265,50 +318,16 @@ int rtw_render_image_device(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, vo
         rc = rtw_render_device(ck, cam, seed, k, n, dst, per * esz, k ? (void*)ck->stream : stream);
         if (rc) return k ? fail(c, rc, ck->err) : rc;
     }
-    if (c->virt) {
-        // test mode (rtw_create_virtual): the gather as device copies on rank 0's
-        // stream, each after its rank's render -- the same slots an RCCL gather
-        // to root 0 fills
-        for (uint32_t k = 1; k < n; ++k) {
-            rtw_ctx* ck = rtw_device_ctx(c, k);
-            HIP_TRY(c, hipEventRecord(c->peer_ev[k - 1], ck->stream));
-            HIP_TRY(c, hipStreamWaitEvent(s0, c->peer_ev[k - 1], 0));
-            HIP_TRY(c, hipMemcpyAsync(static_cast<unsigned char*>(c->d_gather) + (size_t)k * per * esz, ck->d_out,
-                                      per * esz, hipMemcpyDeviceToDevice, s0));
-        }
-    } else {
-        // ONE gather of the packed tiles to rank 0 (RCCL over xGMI), ordered after
-        // each rank's render on that rank's stream
-        const RcclApi& api = rccl_api();
-        const ncclDataType_t dt = c->precision == RTW_F32 ? ncclFloat32 : ncclFloat64;
-        ncclResult_t r = api.group_start();
-        if (r != ncclSuccess) return rccl_fail(c, r, "ncclGroupStart");
-        for (uint32_t k = 0; k < n; ++k) {
-            rtw_ctx* ck = rtw_device_ctx(c, k);
-            r = api.gather(k ? ck->d_out : c->d_gather, k ? nullptr : c->d_gather, per, dt, 0, c->comms[k],
-                           k ? ck->stream : s0);
-            if (r != ncclSuccess) {
-                (void)api.group_end();
-                return rccl_fail(c, r, "ncclGather");
-            }
-        }
-        r = api.group_end();
-        if (r != ncclSuccess) return rccl_fail(c, r, "ncclGroupEnd");
-    }
+    std::vector<const void*> src(n, c->d_gather);
+    for (uint32_t k = 1; k < n; ++k) src[k] = rtw_device_ctx(c, k)->d_out;
+    rc = gather_ranks(c, src, per, esz, s0);
+    if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     // rank 0 un-interleaves the n buffers into the image
     rc = img ? rtw_assemble_tiles(c, c->d_gather, per * esz, n, W, H, d_image, stream) : RTW_OK;
     if (rc) return rc;
-    // every rank's next render waits for this gather + assembly (a peer's
-    // packed tiles are read on s0 in the virtual mode; d_gather always)
-    HIP_TRY(c, hipEventRecord(c->gather_ev, s0));
-    for (uint32_t k = 1; k < n; ++k) {
-        rtw_ctx* ck = rtw_device_ctx(c, k);
-        HIP_TRY(c, hipSetDevice(ck->device));
-        HIP_TRY(c, hipStreamWaitEvent(ck->stream, c->gather_ev, 0));
-    }
-    HIP_TRY(c, hipSetDevice(c->device));
-    c->gather_pending = true;
+    rc = gather_done(c, s0);
+    if (rc) return rc;
     c->stats_ranks = n;
     return RTW_OK;
 }

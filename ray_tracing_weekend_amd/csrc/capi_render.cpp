@@ -2,7 +2,7 @@
 // render is one pass or several (host/render_pass.hpp); a pass is plan
 // (host/render_plan.hpp) -> params -> buffers -> task order (capi_lpt.cpp) ->
 // launch -> bookkeeping.  The one-shot and window entries, the tile assembly
-// and the blocking rtw_render / rtw_render_window.
+// and the blocking rtw_render / rtw_render_window / rtw_render_window_image.
 #include <algorithm>
 
 #include "capi_ctx.hpp"
@@ -29,16 +29,6 @@ int ensure_tile_map(rtw_ctx* c, uint32_t W, uint32_t H, uint32_t rank, uint32_t 
     if (rc) return rc;
     s.tile_map_key = s.serial;
     s.tile_map_rank = rank;
-    return RTW_OK;
-}
-
-// the assembly's map of the active split (host/tiles.hpp tile_slots)
-int ensure_tile_slot(rtw_ctx* c, uint32_t nranks) {
-    SplitState& s = c->split;
-    if (s.d_tile_slot && s.tile_slot_key == s.serial) return RTW_OK;
-    const int rc = upload_map(c, &s.d_tile_slot, &s.tile_slot_cap, rtw::tile_slots(s.rank, nranks));
-    if (rc) return rc;
-    s.tile_slot_key = s.serial;
     return RTW_OK;
 }
 
@@ -132,6 +122,7 @@ int render_pass_t(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t ran
     HIP_TRY(c, hipEventRecord(ev[2], stream));
     // bookkeeping
     ++c->n_renders;
+    c->no_work = false;
     std::vector<uint32_t> tiles;
     c->split.local_tiles(W, H, rank, nranks, tiles);
     const uint64_t before = pass.begin ? 0 : c->last.samples;
@@ -207,7 +198,100 @@ int render_window_t(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t r
     return render_pass_t<R>(c, cam, seed, rank, nranks, nullptr, stream, ps);
 }
 
+// rtw_render_window_image on a multi-device context: every rank folds the
+// window onto its own packed f64 accumulator (rank 0's is its slot of the
+// gather target), continued from the caller's sums; ONE gather, the assembly
+// in f64 whatever the precision, the download.
+template <typename R>
+int render_window_multi_t(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t first, uint32_t n_samples,
+                          double* sums, rtw_stats* stats) {
+    const uint32_t W = cam->image_width, H = cam->image_height, n = rtw_device_count(c);
+    hipStream_t s0 = c->stream;
+    // every rank's window is checked before any rank launches
+    for (uint32_t k = 0; k < n; ++k) {
+        rtw_ctx* ck = rtw_device_ctx(c, k);
+        HIP_TRY(c, hipSetDevice(ck->device));
+        const uint32_t chunk = window_chunk<R>(ck, n_samples, rtw::tiles_for_rank(W, H, k, n));
+        if (first % chunk) {
+            (void)hipSetDevice(c->device);
+            return fail(c, RTW_E_INVALID, "first_sample is not a multiple of the chunk (" + std::to_string(chunk) + ")");
+        }
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (n_samples == 0) return RTW_OK;
+    int rc = check_image_size(c, cam);
+    if (rc) return rc;
+    const size_t per = std::max<size_t>((size_t)rtw::tiles_for_rank(W, H, 0, n) * 64 * 3, 1), img = (size_t)W * H * 3;
+    rc = ensure(c, &c->d_gather, &c->gather_cap, (size_t)n * per * sizeof(double));
+    if (!rc) rc = ensure(c, &c->d_img, &c->img_cap, std::max<size_t>(img * sizeof(double), 64));
+    if (rc) return rc;
+    const uint32_t* slot = nullptr;
+    if (c->split.active(W, H, n)) {
+        rc = ensure_tile_slot(c, n);
+        if (rc) return rc;
+        slot = reinterpret_cast<const uint32_t*>(c->split.d_tile_slot);
+    }
+    // (the previous call's gather + assembly may still read d_gather on another stream)
+    if (c->gather_pending) HIP_TRY(c, hipStreamWaitEvent(s0, c->gather_ev, 0));
+    std::vector<std::vector<double>> packed(n);   // the uploads read them until the streams are waited for
+    std::vector<const void*> src(n, c->d_gather);
+    std::vector<uint32_t> tiles;
+    auto ranks = [&]() -> int {
+        for (uint32_t k = 0; k < n; ++k) {
+            rtw_ctx* ck = rtw_device_ctx(c, k);
+            HIP_TRY(c, hipSetDevice(ck->device));
+            c->split.local_tiles(W, H, k, n, tiles);
+            hipStream_t s = k ? ck->stream : s0;
+            if (k) {
+                // (rank 0's tile count, the most: the gather reads equal-size buffers)
+                const int erc = ensure_accum(ck, rtw::tiles_for_rank(W, H, 0, n));
+                if (erc) return fail(c, erc, ck->err);
+                src[k] = ck->d_accum;
+            }
+            double* acc = k ? reinterpret_cast<double*>(ck->d_accum) : reinterpret_cast<double*>(c->d_gather);
+            const size_t bytes = rtw::packed_bytes((uint32_t)tiles.size(), sizeof(double));
+            if (first && bytes) {
+                packed[k].resize(tiles.size() * 64 * 3);
+                rtw::image_to_packed(sums, W, H, tiles, packed[k].data());
+                HIP_TRY(c, hipMemcpyAsync(acc, packed[k].data(), bytes, hipMemcpyHostToDevice, s));
+            }
+            const int wrc = render_window_t<R>(ck, cam, seed, k, n, first, n_samples, acc, bytes, s);
+            if (wrc) return k ? fail(c, wrc, ck->err) : wrc;
+        }
+        return gather_ranks(c, src, per, sizeof(double), s0);
+    };
+    rc = ranks();
+    if (!rc) rc = hipSetDevice(c->device) == hipSuccess ? RTW_OK : fail(c, RTW_E_DEVICE, "hipSetDevice failed");
+    if (!rc && rtw::launch_assemble(reinterpret_cast<const double*>(c->d_gather), per, n, W, H, slot,
+                                    reinterpret_cast<double*>(c->d_img), s0))
+        rc = fail(c, RTW_E_DEVICE, std::string("assemble launch failed: ") + hipGetErrorString(hipGetLastError()));
+    if (!rc) rc = gather_done(c, s0);
+    if (rc) {
+        // the first error is the call's; no buffer (the uploads' host side included) stays in use
+        for (uint32_t k = 0; k < n; ++k) {
+            rtw_ctx* ck = rtw_device_ctx(c, k);
+            if (hipSetDevice(ck->device) == hipSuccess) (void)hipStreamSynchronize(k ? ck->stream : s0);
+        }
+        (void)hipSetDevice(c->device);
+        return rc;
+    }
+    c->stats_ranks = n;
+    if (img) HIP_TRY(c, hipMemcpyAsync(sums, c->d_img, img * sizeof(double), hipMemcpyDeviceToHost, s0));
+    HIP_TRY(c, hipStreamSynchronize(s0));
+    return fetch_stats(c, stats);
+}
+
 }  // namespace
+
+// the assembly's map of the active split (host/tiles.hpp tile_slots)
+int ensure_tile_slot(rtw_ctx* c, uint32_t nranks) {
+    SplitState& s = c->split;
+    if (s.d_tile_slot && s.tile_slot_key == s.serial) return RTW_OK;
+    const int rc = upload_map(c, &s.d_tile_slot, &s.tile_slot_cap, rtw::tile_slots(s.rank, nranks));
+    if (rc) return rc;
+    s.tile_slot_key = s.serial;
+    return RTW_OK;
+}
 
 size_t device_total(rtw_ctx* c) {
     if (!c->dev_total) {
@@ -298,22 +382,10 @@ int rtw_render_window(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t
     const size_t n = tiles.size() * 64 * 3;
     int rc = ensure_accum(c, (uint32_t)tiles.size());
     if (rc) return rc;
-    const uint32_t tiles_x = rtw::tiles_across(W);
-    // image [H][W][3] <-> packed tiles [lt][ly * 8 + lx][3]
-    auto each_pixel = [&](auto&& f) {
-        for (size_t lt = 0; lt < tiles.size(); ++lt) {
-            const uint32_t tx = tiles[lt] % tiles_x, ty = tiles[lt] / tiles_x;
-            for (uint32_t px = 0; px < 64; ++px) {
-                const uint32_t i = tx * rtw::kTile + (px & 7u), j = ty * rtw::kTile + (px >> 3);
-                if (i < W && j < H) f(((size_t)j * W + i) * 3, (lt * 64 + px) * 3);
-            }
-        }
-    };
+    // image [H][W][3] <-> packed tiles [lt][ly * 8 + lx][3] (host/tiles.hpp)
     std::vector<double> packed(n, 0.0);
     if (first_sample && n_samples && n) {
-        each_pixel([&](size_t img, size_t pk) {
-            for (int k = 0; k < 3; ++k) packed[pk + k] = sums[img + k];
-        });
+        rtw::image_to_packed(sums, W, H, tiles, packed.data());
         HIP_TRY(c, hipMemcpyAsync(c->d_accum, packed.data(), n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     }
     rc = rtw_render_window_device(c, cam, seed, 0, 1, first_sample, n_samples, reinterpret_cast<double*>(c->d_accum),
@@ -325,10 +397,20 @@ int rtw_render_window(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t
     if (n_samples == 0) return RTW_OK;
     if (n) HIP_TRY(c, hipMemcpyAsync(packed.data(), c->d_accum, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    each_pixel([&](size_t img, size_t pk) {
-        for (int k = 0; k < 3; ++k) sums[img + k] = packed[pk + k];
-    });
+    rtw::packed_to_image(packed.data(), W, H, tiles, sums);
     return fetch_stats(c, stats);
+}
+
+int rtw_render_window_image(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t first_sample, uint32_t n_samples,
+                            double* sums, rtw_stats* stats) {
+    if (!c || !cam || !sums) return fail(c, RTW_E_INVALID, "bad argument");
+    if (!c->multi) return rtw_render_window(c, cam, seed, first_sample, n_samples, sums, stats);
+    if (!c->has_scene) return fail(c, RTW_E_NO_SCENE, "rtw_set_scene was not called");
+    if ((uint64_t)first_sample + n_samples > 0xFFFFFFFFull)
+        return fail(c, RTW_E_INVALID, "first_sample + n_samples overflows");
+    return by_precision(c, [&](auto r) {
+        return render_window_multi_t<decltype(r)>(c, cam, seed, first_sample, n_samples, sums, stats);
+    });
 }
 
 int rtw_render(rtw_ctx* c, const rtw_camera* cam, const rtw_scene* scene, uint64_t seed, double* out_sum,

@@ -1,5 +1,5 @@
 // render_adaptive.cpp -- Camera::render_adaptive of the C++ host mirror
-// (rtw_host.hpp) through rtw_render_adaptive; the pass plan and the stop rule
+// (rtw_host.hpp) through rtw_render_adaptive_image; the pass plan and the stop rule
 // are render_adaptive.hpp's.  Its own unit, as render_windows.cpp: programs
 // that link rtw_host.cpp without a device need no more entry points than
 // Camera::render uses.
@@ -17,19 +17,18 @@ std::vector<std::vector<SampledColour>> Camera::render_adaptive(const HittableLi
         throw Error(RTW_E_INVALID, std::string("render_adaptive: ") + why);
     FlatScene flat = flatten(world, lights);
     rtw_scene view = flat.view();
-    rtw_ctx* ctx = rtw_create(opt.device, opt.precision);
-    if (!ctx) throw Error(RTW_E_DEVICE, "rtw_create failed (no gfx950 device?)");
+    rtw_ctx* ctx = create_context(opt);
     rtw_set_accel(ctx, opt.accel);
     int rc = rtw_set_scene(ctx, &view);
     const uint32_t W = c_.image_width, H = c_.image_height;
     std::vector<double> sums((size_t)W * H * 3, 0.0);
     std::vector<uint32_t> counts((size_t)W * H, 0);
     if (rc == RTW_OK)
-        rc = rtw_render_adaptive(ctx, &c_, opt.seed, min_samples, max_samples, window, tolerance, sums.data(),
+        rc = rtw_render_adaptive_image(ctx, &c_, opt.seed, min_samples, max_samples, window, tolerance, sums.data(),
                                  counts.data(), nullptr);
     std::string err = rc ? rtw_last_error(ctx) : "";
     rtw_destroy(ctx);
-    if (rc != RTW_OK) throw Error(rc, "rtw_render_adaptive: " + err);
+    if (rc != RTW_OK) throw Error(rc, "rtw_render_adaptive_image: " + err);
     std::vector<std::vector<SampledColour>> out(H, std::vector<SampledColour>(W));
     for (uint32_t j = 0; j < H; ++j)
         for (uint32_t i = 0; i < W; ++i) {

@@ -1,5 +1,5 @@
 // render_windows.cpp -- Camera::render_windows of the C++ host mirror
-// (rtw_host.hpp): the progressive render through rtw_render_window.  Its own
+// (rtw_host.hpp): the progressive render through rtw_render_window_image.  Its own
 // unit, so that programs that link rtw_host.cpp without a device (the CPU
 // checks) need no more entry points than Camera::render uses.
 #include <algorithm>
@@ -14,8 +14,7 @@ std::vector<std::vector<SampledColour>> Camera::render_windows(
     if (window == 0) throw Error(RTW_E_INVALID, "render_windows: window must be >= 1");
     FlatScene flat = flatten(world, lights);
     rtw_scene view = flat.view();
-    rtw_ctx* ctx = rtw_create(opt.device, opt.precision);
-    if (!ctx) throw Error(RTW_E_DEVICE, "rtw_create failed (no gfx950 device?)");
+    rtw_ctx* ctx = create_context(opt);
     rtw_set_accel(ctx, opt.accel);
     int rc = rtw_set_scene(ctx, &view);
     const uint32_t W = c_.image_width, H = c_.image_height, spp = c_.samples_per_pixel;
@@ -23,14 +22,14 @@ std::vector<std::vector<SampledColour>> Camera::render_windows(
     uint32_t done = 0;
     while (rc == RTW_OK && done < spp) {
         const uint32_t n = std::min(window, spp - done);
-        rc = rtw_render_window(ctx, &c_, opt.seed, done, n, sums.data(), nullptr);
+        rc = rtw_render_window_image(ctx, &c_, opt.seed, done, n, sums.data(), nullptr);
         if (rc != RTW_OK) break;
         done += n;
         if (on_window && !on_window(done, sums)) break;
     }
     std::string err = rc ? rtw_last_error(ctx) : "";
     rtw_destroy(ctx);
-    if (rc != RTW_OK) throw Error(rc, "rtw_render_window: " + err);
+    if (rc != RTW_OK) throw Error(rc, "rtw_render_window_image: " + err);
     std::vector<std::vector<SampledColour>> out(H, std::vector<SampledColour>(W));
     for (uint32_t j = 0; j < H; ++j)
         for (uint32_t i = 0; i < W; ++i) {

@@ -317,11 +317,7 @@ Camera CameraBuilder::build() const {
     return Camera(c);
 }
 
-std::vector<std::vector<SampledColour>> Camera::render(const HittableList& world,
-                                                       const HittableList& lights,
-                                                       const RenderOptions& opt) const {
-    FlatScene flat = flatten(world, lights);
-    rtw_scene view = flat.view();
+rtw_ctx* create_context(const RenderOptions& opt) {
     rtw_ctx* ctx = nullptr;
     if (opt.device_mask) {
         // the mask's error code: RTW_E_INVALID (empty, or a device that is not
@@ -335,6 +331,15 @@ std::vector<std::vector<SampledColour>> Camera::render(const HittableList& world
         ctx = rtw_create(opt.device, opt.precision);
         if (!ctx) throw Error(RTW_E_DEVICE, "rtw_create failed (no gfx950 device?)");
     }
+    return ctx;
+}
+
+std::vector<std::vector<SampledColour>> Camera::render(const HittableList& world,
+                                                       const HittableList& lights,
+                                                       const RenderOptions& opt) const {
+    FlatScene flat = flatten(world, lights);
+    rtw_scene view = flat.view();
+    rtw_ctx* ctx = create_context(opt);
     rtw_set_accel(ctx, opt.accel);
     const uint32_t W = c_.image_width, H = c_.image_height;
     std::vector<double> sums((size_t)W * H * 3);

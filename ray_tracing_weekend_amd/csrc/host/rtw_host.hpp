@@ -215,6 +215,10 @@ struct RenderOptions {
     int accel = RTW_ACCEL_AUTO;
 };
 
+// The context the options ask for: one device, or one rank per bit of
+// device_mask.  Throws Error; the caller destroys the context.
+rtw_ctx* create_context(const RenderOptions& opt);
+
 class Camera {
    public:
     explicit Camera(const rtw_camera& c) : c_(c) {}
@@ -229,8 +233,9 @@ class Camera {
                                                          const RenderOptions& opt = {}) const {
         return render(world, lights, opt);
     }
-    // The same render `window` samples at a time (rtw_render_window on one
-    // device; opt.device_mask is not used): after each window on_window(samples
+    // The same render `window` samples at a time (rtw_render_window_image: with
+    // opt.device_mask every device renders its tiles of each window): after each
+    // window on_window(samples
     // done, the running sums [H][W][3], j = 0 the bottom row) is called; false
     // from it stops the render there.  Returns the sums so far as render()
     // does -- after the last window render()'s image bit for bit.  Defined in
@@ -239,7 +244,8 @@ class Camera {
         const HittableList& world, const HittableList& lights, uint32_t window,
         const std::function<bool(uint32_t, const std::vector<double>&)>& on_window,
         const RenderOptions& opt = {}) const;
-    // Adaptive sampling (rtw_render_adaptive, include/rtw.h): every 8x8 tile
+    // Adaptive sampling (rtw_render_adaptive_image, include/rtw.h; with
+    // opt.device_mask over every device, the same result): every 8x8 tile
     // takes between min_samples and max_samples samples, `window` at a time,
     // and stops once its pixels' displayed values are within `tolerance`
     // (standard error).  Each SampledColour carries its pixel's own sample

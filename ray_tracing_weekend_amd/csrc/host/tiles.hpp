@@ -1,6 +1,7 @@
 // tiles.hpp -- the 8x8 tile arithmetic of the rank split: tile counts, the
-// tiles of a rank (a dealt split or the round robin), the assembly's slot map
-// and the deal itself.  Host only, no HIP call.
+// tiles of a rank (a dealt split or the round robin), the image <-> a rank's
+// packed tiles, the assembly's slot map and the deal itself.  Host only, no HIP
+// call.
 #pragma once
 
 #include <stddef.h>
@@ -51,6 +52,39 @@ inline uint64_t tile_pixels(uint32_t W, uint32_t H, const std::vector<uint32_t>&
         px += (uint64_t)std::min(kTile, W - tx * kTile) * std::min(kTile, H - ty * kTile);
     }
     return px;
+}
+
+// f(the pixel's offset in the image [H][W][3], its offset in the packed tiles
+// [lt][ly * 8 + lx][3]) for every pixel of `tiles` (a rank's, in packed order)
+// that lies inside the image
+template <typename F>
+inline void each_packed_pixel(uint32_t W, uint32_t H, const std::vector<uint32_t>& tiles, F&& f) {
+    const uint32_t tiles_x = tiles_across(W);
+    for (size_t lt = 0; lt < tiles.size(); ++lt) {
+        const uint32_t tx = tiles[lt] % tiles_x, ty = tiles[lt] / tiles_x;
+        for (uint32_t px = 0; px < 64; ++px) {
+            const uint32_t i = tx * kTile + (px & 7u), j = ty * kTile + (px >> 3);
+            if (i < W && j < H) f(((size_t)j * W + i) * 3, (lt * 64 + px) * 3);
+        }
+    }
+}
+
+// the image [H][W][3] -> a rank's packed tiles (tiles.size() * 64 * 3 values;
+// pixels outside the image: 0)
+inline void image_to_packed(const double* img, uint32_t W, uint32_t H, const std::vector<uint32_t>& tiles,
+                            double* packed) {
+    std::fill(packed, packed + tiles.size() * 64 * 3, 0.0);
+    each_packed_pixel(W, H, tiles, [&](size_t at, size_t pk) {
+        for (int k = 0; k < 3; ++k) packed[pk + k] = img[at + k];
+    });
+}
+
+// a rank's packed tiles -> its pixels of the image [H][W][3] (the others untouched)
+inline void packed_to_image(const double* packed, uint32_t W, uint32_t H, const std::vector<uint32_t>& tiles,
+                            double* img) {
+    each_packed_pixel(W, H, tiles, [&](size_t at, size_t pk) {
+        for (int k = 0; k < 3; ++k) img[at + k] = packed[pk + k];
+    });
 }
 
 // the assembly's map of a split: global tile T -> lt * n + rank (the round

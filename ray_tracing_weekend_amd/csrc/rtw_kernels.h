@@ -435,5 +435,16 @@ int launch_compact_tiles(const uint32_t* flags, uint32_t n_tiles, uint32_t W, ui
 // the state by tile -> image-order sums [H][W][3] and counts [H][W]
 int launch_unpack_adaptive(const double* sums, const uint32_t* counts, uint32_t W, uint32_t H, double* img,
                            uint32_t* img_counts, hipStream_t stream);
+// A rank's share of an adaptive render travels to rank 0 as one record per
+// tile: the tile's 64 * 3 colour sums, then its count in the low word of one
+// more double (the high word 0).
+constexpr size_t kAdaptiveRecord = 64 * 3 + 1;   // doubles
+// the state of the n_tiles global tiles of `tiles` (ascending) -> records, in that order
+int launch_pack_adaptive(const uint32_t* tiles, uint32_t n_tiles, const double* sums, const uint32_t* counts,
+                         double* records, hipStream_t stream);
+// The ranks' records (nranks buffers, rank_stride doubles apart) -> image-order
+// sums [H][W][3] and counts [H][W]; slot as launch_assemble's.
+int launch_assemble_adaptive(const double* ranks, size_t rank_stride, uint32_t nranks, uint32_t W, uint32_t H,
+                             const uint32_t* slot, double* img, uint32_t* img_counts, hipStream_t stream);
 
 }  // namespace rtw

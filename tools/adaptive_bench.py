@@ -16,8 +16,15 @@ by a host clock that ends in a device synchronise:
       read-back, the compaction and the statistic in the fold -- so the two
       Msamples/s figures are the machinery's cost.
 
+  --virtual N: every setting on N virtual ranks of the one GPU
+      (rtw_create_virtual; the adaptive settings through
+      rtw_render_adaptive_image_device).  Against the same run without it this is
+      the cost of the n-rank orchestration, the gather and the assembly; the
+      ranks share the GPU, so it is no scaling figure.
+
     python tools/adaptive_bench.py [--tolerances 0,0.00390625,0.0078125,0.015625] [--precision f64]
                                    [--size 1200x800] [--samples 32,32,500] [--ref-spp 2000] [--rounds 1]
+                                   [--virtual N]
     python tools/adaptive_bench.py --one SETTING --ref FILE      (internal: one measurement)
 """
 import argparse
@@ -60,15 +67,16 @@ def reference(path, precision, size, ref_spp):
         np.save(path, np.sqrt(sums / ref_spp))
 
 
-def one(setting, precision, steps, warmup, size, samples, ref_path):
+def one(setting, precision, steps, warmup, size, samples, ref_path, virtual=0):
     import numpy as np
     import torch
     mn, win, mx = samples
     rtw, prec, scene, cam = _setup(precision, size, mx)
     w, h = size
     ref = np.load(ref_path)
-    out = {"setting": setting, "precision": precision, "size": f"{w}x{h}", "min_window_max": list(samples)}
-    with rtw.Renderer(device=0, precision=prec) as r:
+    out = {"setting": setting, "precision": precision, "size": f"{w}x{h}", "min_window_max": list(samples),
+           "virtual_ranks": virtual}
+    with rtw.Renderer(device=0, precision=prec, virtual_ranks=virtual or None) as r:
         if setting == "window":
             r.set_tuning("window", win)
         r.set_scene(scene)
@@ -124,6 +132,7 @@ def main():
     ap.add_argument("--size", default="1200x800")
     ap.add_argument("--samples", default="32,32,500", help="min,window,max")
     ap.add_argument("--ref-spp", type=int, default=2000)
+    ap.add_argument("--virtual", type=int, default=0, help="N virtual ranks on the one GPU (0: a one-device context)")
     ap.add_argument("--one")
     ap.add_argument("--ref")
     a = ap.parse_args()
@@ -133,12 +142,12 @@ def main():
         reference(a.ref, a.precision, size, a.ref_spp)
         return
     if a.one is not None:
-        one(a.one, a.precision, a.steps, a.warmup, size, samples, a.ref)
+        one(a.one, a.precision, a.steps, a.warmup, size, samples, a.ref, a.virtual)
         return
     with tempfile.TemporaryDirectory() as d:
         ref = os.path.join(d, "ref.npy")
         common = ["--precision", a.precision, "--steps", str(a.steps), "--warmup", str(a.warmup), "--size", a.size,
-                  "--samples", a.samples, "--ref-spp", str(a.ref_spp), "--ref", ref]
+                  "--samples", a.samples, "--ref-spp", str(a.ref_spp), "--ref", ref, "--virtual", str(a.virtual)]
         subprocess.run([sys.executable, __file__, "--one", "reference", *common], check=True, timeout=900)
         for rd in range(a.rounds):
             for setting in ["fixed", "window", *a.tolerances.split(",")]:
