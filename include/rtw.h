@@ -536,6 +536,72 @@ int rtw_get_timings(rtw_ctx *ctx, float *render_ms, float *total_ms, int max);
  * exact machine code that ran (render_kernel<R, kernel, options>). */
 int rtw_last_kernel(const rtw_ctx *ctx);
 
+/* ---- batched ray queries: Hittable::hit and the light list's pdf_value ---
+ * The reference's other public surface, the Hittable trait (shared/src/
+ * hittable.rs:172-182), against the scene staged by rtw_set_scene:
+ *   closest hit   world.hit(&r, t_min..=INFINITY) of the HittableList /
+ *                 BoundedVolumeHierarchy (hittable_collections/bvh.rs:164-188)
+ *                 for n rays, each answered with a HitRecord::new
+ *                 (hittable.rs:100-129);
+ *   light pdf     HittableList::pdf_value(origin, direction) of the light list
+ *                 (hittable_list.rs:408-412), the RTW_LIGHTS_BVH_LEAF form
+ *                 included, NaN where the reference gives NaN (an origin
+ *                 inside a light sphere; an empty list's 0 / 0).
+ * A query runs the traversal a render of the scene would run under the same
+ * tuning keys (accel, bvh_kind, lds, bvh_lds_max, robust, light_grid,
+ * light_bvh_min), through the same device code.  RTW_F64: bit-identical to
+ * the reference's f64 arithmetic.  RTW_F32: the plain f32 arithmetic of the
+ * speed mode -- the render's f64 hit-point refinement (tuning hit64) is not
+ * part of a query.  Queries keep their own buffers and counters: a render
+ * before and after one is unchanged.
+ *
+ *   rays: n x 6 {ox, oy, oz, dx, dy, dz} in the context's precision (float
+ *         or double); the direction need not be normalised
+ *   hits: n x 9 {t, p xyz, normal xyz (against the ray: front-face adjusted),
+ *         u, v}, same precision
+ *   ids : n x 4 int32 {object id, material id, front face 0 / 1, RTW_PRIM_*}.
+ *         Object ids count planes, then quads, cuboids, spheres, each in scene
+ *         order (the ids of rtw_stats and the oracle).
+ *   A miss: object id -1, every other field of both rows 0.
+ * Equal t goes to the lowest object id.  A cuboid hit reports what the render
+ * uses (entities/transformations.rs:14-29): the world-space point with the
+ * object-space normal, front face and UV.
+ * t_min: one scalar per call, finite and >= 0 (the reference passes
+ * f64::EPSILON from the integrator, 0 from pdf_value); the upper end is
+ * always +inf, the only one the reference passes.
+ *
+ * Errors: RTW_E_INVALID for a NULL context, a NULL array with n > 0, a buffer
+ * that is too small, a negative / NaN / infinite t_min; RTW_E_NO_SCENE before
+ * rtw_set_scene; RTW_E_UNSUPPORTED on a multi-device or virtual-rank context
+ * (a query has no tiles to split).  n = 0 is RTW_OK and launches nothing.
+ * The host forms are synchronous; the device forms enqueue on the caller's
+ * stream as rtw_render_device does (NULL: the context's own). */
+#define RTW_PRIM_PLANE 0
+#define RTW_PRIM_QUAD 1
+#define RTW_PRIM_CUBOID 2
+#define RTW_PRIM_SPHERE 3
+int rtw_hit_rays(rtw_ctx *ctx, const void *rays, uint64_t n, double t_min, void *hits, int32_t *ids);
+int rtw_hit_rays_device(rtw_ctx *ctx, const void *d_rays, uint64_t n, double t_min, void *d_hits,
+                        size_t hits_bytes, int32_t *d_ids, size_t ids_bytes, void *stream);
+/* pdf: n values of the context's precision */
+int rtw_light_pdf_rays(rtw_ctx *ctx, const void *rays, uint64_t n, void *pdf);
+int rtw_light_pdf_rays_device(rtw_ctx *ctx, const void *d_rays, uint64_t n, void *d_pdf, size_t pdf_bytes,
+                              void *stream);
+typedef struct rtw_query_stats {
+    uint64_t rays;                /* rays of the last query */
+    uint64_t hits;                /* ... that hit something (closest hit) */
+    uint64_t node_visits;         /* BVH inner nodes entered */
+    uint64_t sphere_tests;        /* ray-sphere tests (the brute-force sweep: rays x spheres) */
+    uint64_t light_tests;         /* (ray, light) pairs the light pdf tested */
+    uint32_t kernel;              /* closest hit: the world that ran, as rtw_stats.kernel;
+                                     light pdf: 0 linear list, 1 light BVH, 2 light grid,
+                                     3 mixed list (quads / default entries) */
+    uint32_t is_light_pdf;        /* 1: the last query was a light pdf */
+    double kernel_ms;             /* device time of the query kernel (HIP events) */
+} rtw_query_stats;
+/* Counters of the last query (waits for it); RTW_E_INVALID before the first. */
+int rtw_get_query_stats(rtw_ctx *ctx, rtw_query_stats *stats);
+
 /* ---- scenes::simple (scenes/src/lib.rs:155-233) ----------------------- */
 /* The library owns the arrays; view them through rtw_world_scene(). grid_n =
  * 11 is the reference scene; larger n gives the synthetic C3/C5 fields. */

@@ -208,6 +208,27 @@ class HittableList:                          # hittable_collections/hittable_lis
     def __len__(self):
         return len(self.objects)
 
+    def hit(self, rays, t_min: float | None = None, *, lights=None, precision: int = RTW_F64,
+            device: int = 0, accel: int = RTW_ACCEL_AUTO):
+        """Hittable::hit of this list as the world (hittable.rs:172-182), for
+        n rays [n, 6] {origin, direction} over t_min..=INFINITY: (hits [n, 9],
+        ids [n, 4]) as Renderer.hit_rays gives them.  Flattens and stages the
+        scene as Camera.render does; keep a Renderer for repeated queries."""
+        with Renderer(device=device, precision=precision) as r:
+            r.set_accel(accel)
+            r.set_scene(flatten(self, lights if lights is not None else HittableList()))
+            return r.hit_rays(rays, t_min)
+
+    def pdf_value(self, rays, *, world=None, precision: int = RTW_F64, device: int = 0,
+                  accel: int = RTW_ACCEL_AUTO):
+        """HittableList::pdf_value of this list as the light list
+        (hittable_list.rs:408-412; a BoundedVolumeHierarchy: its leaf form) for
+        n (origin, direction) pairs [n, 6]: the pdfs [n]."""
+        with Renderer(device=device, precision=precision) as r:
+            r.set_accel(accel)
+            r.set_scene(flatten(world if world is not None else HittableList(), self))
+            return r.light_pdf(rays)
+
 
 class BoundedVolumeHierarchy(HittableList):  # hittable_collections/bvh.rs:106-143 (::from(list))
     """The reference's BVH over a list: as the world it gives the list's
@@ -778,6 +799,81 @@ class Renderer:
     def get_stats(self) -> "_capi.rtw_stats":
         self._check(_lib.rtw_get_stats(self.ctx, C.byref(self.stats)), "rtw_get_stats")
         return self.stats
+
+    # ---- batched ray queries (rtw_hit_rays / rtw_light_pdf_rays)
+    def _query_rays(self, rays, what):
+        """(rays as [n, 6] of the context's precision, is_torch).  numpy input is
+        converted; a torch tensor must be on this device, contiguous and of the
+        context's precision already (no silent copy of device memory)."""
+        np_dtype = np.float32 if self.precision == RTW_F32 else np.float64
+        if type(rays).__module__.split(".")[0] == "torch":
+            import torch
+            want = torch.float32 if self.precision == RTW_F32 else torch.float64
+            if rays.dtype != want:
+                raise RenderError(_capi.RTW_E_INVALID, f"{what}: tensor dtype {rays.dtype}, the context's is {want}")
+            if not rays.is_cuda or rays.device.index != self.device:
+                raise RenderError(_capi.RTW_E_INVALID, f"{what}: the tensor is not on device {self.device}")
+            if rays.dim() != 2 or rays.shape[1] != 6 or not rays.is_contiguous():
+                raise RenderError(_capi.RTW_E_INVALID, f"{what}: rays must be a contiguous [n, 6] tensor")
+            return rays, True
+        a = np.ascontiguousarray(np.asarray(rays, np_dtype))
+        if a.ndim != 2 or a.shape[1] != 6:
+            raise RenderError(_capi.RTW_E_INVALID, f"{what}: rays must be [n, 6] {{origin, direction}}")
+        return a, False
+
+    def hit_rays(self, rays, t_min: float | None = None):
+        """world.hit(&r, t_min..=INFINITY) of the staged scene for n rays
+        [n, 6] {origin, direction}: (hits [n, 9] {t, p, normal (front-face
+        adjusted), u, v}, ids [n, 4] int32 {object id or -1, material id, front
+        face, RTW_PRIM_*}); a miss has object -1 and zeros.  t_min defaults to
+        f64::EPSILON, the integrator's.  numpy in, numpy out (the host entry);
+        a torch tensor on the GPU goes through the device entry on torch's
+        current stream, without a host copy, and torch tensors come back."""
+        t_min = 2.220446049250313e-16 if t_min is None else float(t_min)
+        r, is_torch = self._query_rays(rays, "hit_rays")
+        n = int(r.shape[0])
+        if is_torch:
+            import torch
+            hits = torch.zeros((n, 9), dtype=r.dtype, device=r.device)
+            ids = torch.zeros((n, 4), dtype=torch.int32, device=r.device)
+            stream = _torch_stream(self.device)
+            self._check(_lib.rtw_hit_rays_device(self.ctx, C.c_void_p(r.data_ptr()), n, t_min,
+                                                 C.c_void_p(hits.data_ptr()), hits.numel() * hits.element_size(),
+                                                 C.c_void_p(ids.data_ptr()), ids.numel() * 4,
+                                                 C.c_void_p(stream) if stream else None), "rtw_hit_rays_device")
+            return hits, ids
+        hits = np.zeros((n, 9), r.dtype)
+        ids = np.zeros((n, 4), np.int32)
+        self._check(_lib.rtw_hit_rays(self.ctx, r.ctypes.data_as(C.c_void_p), n, t_min,
+                                      hits.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p)), "rtw_hit_rays")
+        return hits, ids
+
+    def light_pdf(self, rays):
+        """lights.pdf_value(origin, direction) of the staged light list for n
+        pairs [n, 6]: the pdfs [n] (NaN where the reference's is: an origin
+        inside a light sphere, an empty list).  numpy / torch as hit_rays."""
+        r, is_torch = self._query_rays(rays, "light_pdf")
+        n = int(r.shape[0])
+        if is_torch:
+            import torch
+            pdf = torch.zeros((n,), dtype=r.dtype, device=r.device)
+            stream = _torch_stream(self.device)
+            self._check(_lib.rtw_light_pdf_rays_device(self.ctx, C.c_void_p(r.data_ptr()), n,
+                                                       C.c_void_p(pdf.data_ptr()), pdf.numel() * pdf.element_size(),
+                                                       C.c_void_p(stream) if stream else None),
+                        "rtw_light_pdf_rays_device")
+            return pdf
+        pdf = np.zeros(n, r.dtype)
+        self._check(_lib.rtw_light_pdf_rays(self.ctx, r.ctypes.data_as(C.c_void_p), n,
+                                            pdf.ctypes.data_as(C.c_void_p)), "rtw_light_pdf_rays")
+        return pdf
+
+    def get_query_stats(self) -> "_capi.rtw_query_stats":
+        """Counters of the last query (rtw_get_query_stats): rays, hits, node
+        visits, sphere tests, light tests, the world / light path that ran."""
+        st = _capi.rtw_query_stats()
+        self._check(_lib.rtw_get_query_stats(self.ctx, C.byref(st)), "rtw_get_query_stats")
+        return st
 
 
 class _RankView(Renderer):

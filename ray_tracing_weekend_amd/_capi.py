@@ -81,6 +81,17 @@ class rtw_stats(C.Structure):
     ]
 
 
+RTW_PRIM_PLANE, RTW_PRIM_QUAD, RTW_PRIM_CUBOID, RTW_PRIM_SPHERE = 0, 1, 2, 3
+
+
+class rtw_query_stats(C.Structure):
+    _fields_ = [
+        ("rays", C.c_uint64), ("hits", C.c_uint64), ("node_visits", C.c_uint64),
+        ("sphere_tests", C.c_uint64), ("light_tests", C.c_uint64),
+        ("kernel", C.c_uint32), ("is_light_pdf", C.c_uint32), ("kernel_ms", C.c_double),
+    ]
+
+
 # (name, restype, argtypes) for every entry point declared in include/rtw.h
 PROTOTYPES = [
     ("rtw_abi_version", C.c_int, []),
@@ -137,6 +148,13 @@ PROTOTYPES = [
     ("rtw_get_stats_rank", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(rtw_stats)]),
     ("rtw_get_timings", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]),
     ("rtw_last_kernel", C.c_int, [C.c_void_p]),
+    ("rtw_hit_rays", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_double, C.c_void_p, C.c_void_p]),
+    ("rtw_hit_rays_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_double, C.c_void_p, C.c_size_t,
+                                      C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("rtw_light_pdf_rays", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    ("rtw_light_pdf_rays_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t,
+                                            C.c_void_p]),
+    ("rtw_get_query_stats", C.c_int, [C.c_void_p, C.POINTER(rtw_query_stats)]),
     ("rtw_scene_simple", C.c_void_p, [C.c_uint64, C.c_int]),
     ("rtw_world_scene", C.POINTER(rtw_scene), [C.c_void_p]),
     ("rtw_world_camera_builder", None, [C.c_void_p, C.POINTER(rtw_camera_builder)]),

@@ -44,6 +44,7 @@ void rtw_destroy(rtw_ctx* c) {
     if (c->gather_ev) (void)hipEventDestroy(c->gather_ev);
     if (c->d_gather) (void)hipFree(c->d_gather);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    destroy_query(c);
     if (c->d_scene) (void)hipFree(c->d_scene);
     if (c->d_partial) (void)hipFree(c->d_partial);
     if (c->d_accum) (void)hipFree(c->d_accum);

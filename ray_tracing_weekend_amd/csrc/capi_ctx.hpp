@@ -1,5 +1,5 @@
 // capi_ctx.hpp -- private to the C-ABI units (capi.cpp, capi_render.cpp,
-// capi_lpt.cpp, capi_adaptive.cpp, capi_multi.cpp): the context behind
+// capi_lpt.cpp, capi_adaptive.cpp, capi_multi.cpp, capi_query.cpp): the context behind
 // include/rtw.h's rtw_ctx and the helpers they share.
 #pragma once
 
@@ -141,6 +141,9 @@ struct rtw_ctx {
     uint32_t stats_ranks = 1;
     // the last multi-device render gave this rank no tile: its stats are those of no work
     bool no_work = false;
+    // batched ray queries (capi_query.cpp): their own buffers, counters and events,
+    // allocated by the first query -- nothing of the render's is touched
+    struct QueryState* query = nullptr;
 };
 
 static inline int fail(rtw_ctx* c, int code, const std::string& msg) {
@@ -253,3 +256,5 @@ int gather_ranks(rtw_ctx* c, const std::vector<const void*>& src, size_t count, 
 int gather_done(rtw_ctx* c, hipStream_t s0);
 // capi_multi.cpp: rtw_destroy's part for the ranks of a multi-device context
 void destroy_ranks(rtw_ctx* c);
+// capi_query.cpp: rtw_destroy's part for the query state (the context's device is current)
+void destroy_query(rtw_ctx* c);

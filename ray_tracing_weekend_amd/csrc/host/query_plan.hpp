@@ -1,0 +1,31 @@
+// query_plan.hpp -- what a batched ray query launches (rtw_hit_rays /
+// rtw_light_pdf_rays): the world, the test form, the traversal stack and the
+// dynamic LDS of hit_rays_kernel, and the light path of light_pdf_rays_kernel.
+// A query runs the traversal a render of the scene would run under the same
+// tuning keys: the world and the light path are render_plan.hpp plan_world's.
+// Host only, no HIP call.
+#pragma once
+
+#include "../query_kernels.h"
+#include "render_plan.hpp"
+
+namespace rtw {
+
+struct QueryPlan {
+    int accel = RTW_ACCEL_BRUTE;        // RTW_ACCEL_AUTO resolved
+    int world = kWorldLds;              // WorldMode of hit_rays_kernel
+    uint32_t robust = 0;                // f32: the closest-approach sphere / light tests
+    uint32_t stack = 1;                 // traversal stack entries per lane (BVH worlds)
+    size_t hit_lds = kQueryLdsMin;      // dynamic LDS of hit_rays_kernel
+    int light_path = kLightLinear;      // LightPath of light_pdf_rays_kernel
+    uint32_t light_stack = 1;           // the light BVH's stack entries per lane
+    size_t light_lds = kQueryLdsMin;    // dynamic LDS of light_pdf_rays_kernel
+    int err = RTW_OK;
+    const char* err_text = "";
+};
+
+// A query has no camera: knob robust = 2 judges the scene's scale from the origin.
+template <typename R>
+QueryPlan plan_query(const RenderKnobs& k, const DevScene<R>& sc, const SceneScale& scale);
+
+}  // namespace rtw

@@ -71,33 +71,12 @@ static bool scene_has_prims(const DevScene<R>& sc) {
     return sc.n_quads || sc.n_boxes || sc.lref || sc.emissive;
 }
 
+// The world decision (render_plan.hpp plan_world): the accelerator, the world
+// query and its traversal stack, the f32 test form, the light path and the
+// kernel options, with the render kernel's dynamic LDS.
 template <typename R>
-RenderPlan plan_render(const RenderKnobs& k, const DevScene<R>& sc, const rtw_camera& cam, uint32_t n_local_tiles,
-                       uint32_t chunk, const SceneScale& scale) {
-    RenderPlan p;
-    const uint32_t spp = cam.samples_per_pixel;
-    p.chunk = chunk;
-    p.n_chunks = spp ? (spp + chunk - 1) / chunk : 0;
-    uint32_t group = k.group;
-    if (group == 0) {
-        // Persistent waves (default) have no per-task drain; a task boundary
-        // mixes two tiles' items in the wave (less coherent), the launch's tail
-        // grows with the task size.  Longest tiles first leaves cheap tiles
-        // for the end, so ~2^17 tasks (~32 per resident wave): C2 split over
-        // 1 / 2 / 4 / 8 ranks -> 32 / 28 / 15 / 8 chunks per task (N = 1:
-        // group 32 93.7 ms vs 16 94.4, 4 104.4; an 8-way share: 8 13.2 ms vs
-        // 4 13.6).  One task per wave instead pays a drain per task: ~2^17.
-        constexpr uint32_t kMinAutoGroup = 4, kMaxAutoGroup = 32;
-        const uint64_t target = k.target_tasks ? k.target_tasks : kAutoTasks;
-        const uint64_t n_groups = n_local_tiles ? (target + n_local_tiles - 1) / n_local_tiles : 1;
-        group = (uint32_t)((p.n_chunks + n_groups - 1) / std::max<uint64_t>(n_groups, 1));
-        group = std::max(kMinAutoGroup, std::min(group, kMaxAutoGroup));
-    }
-    // at most 4096 chunks per task: the kernel divides item indices q < 64 * group
-    // by the group with a multiply-high by ceil(2^32 / group), exact while 64 group^2 < 2^32
-    p.group = std::max<uint32_t>(1, std::min<uint32_t>(std::min<uint32_t>(group, 4096u), std::max<uint32_t>(p.n_chunks, 1)));
-    p.n_groups = p.n_chunks ? (p.n_chunks + p.group - 1) / p.group : 0;
-    p.n_tasks = n_local_tiles * p.n_groups;
+void plan_world(const RenderKnobs& k, const DevScene<R>& sc, const double center[3], const SceneScale& scale,
+                RenderPlan& p) {
     const size_t lds = (size_t)(sc.n_sph + sc.n_lights) * sizeof(R4<R>);
     p.accel = k.accel == RTW_ACCEL_AUTO ? k.auto_accel : k.accel;
     if (p.accel == RTW_ACCEL_AUTO) p.accel = sc.n_sph >= 64 ? RTW_ACCEL_BVH : RTW_ACCEL_BRUTE;
@@ -109,7 +88,7 @@ RenderPlan plan_render(const RenderKnobs& k, const DevScene<R>& sc, const rtw_ca
     // rounding once (distance / radius)^2 * 2^-24 is no longer small (C3/C5
     // seen from afar); the closest-approach form is then used.
     {
-        const double cx = (double)(R)cam.center[0], cy = (double)(R)cam.center[1], cz = (double)(R)cam.center[2];
+        const double cx = (double)(R)center[0], cy = (double)(R)center[1], cz = (double)(R)center[2];
         const double far = std::max(scale.extent, sqrt(cx * cx + cy * cy + cz * cz));
         const double rel = std::isfinite(scale.min_radius) ? (far / scale.min_radius) * (far / scale.min_radius) * 5.96e-8
                                                            : 0.0;
@@ -183,7 +162,7 @@ RenderPlan plan_render(const RenderKnobs& k, const DevScene<R>& sc, const rtw_ca
         } else {
             p.err = RTW_E_UNSUPPORTED;
             p.err_text = "BVH deeper than the kernel's traversal stack";
-            return p;
+            return;
         }
     }
     // textured scenes have kernels for the brute-force and binary while-while worlds only
@@ -197,7 +176,7 @@ RenderPlan plan_render(const RenderKnobs& k, const DevScene<R>& sc, const rtw_ca
         if (p.stack > kBvhStack) {
             p.err = RTW_E_UNSUPPORTED;
             p.err_text = "BVH deeper than the kernel's traversal stack";
-            return p;
+            return;
         }
     }
     // The launch's dynamic LDS: the brute-force world in LDS and the tree in LDS
@@ -208,8 +187,38 @@ RenderPlan plan_render(const RenderKnobs& k, const DevScene<R>& sc, const rtw_ca
     if (!dev::variant_exists(!f32, p.world, p.opts)) {
         p.err = RTW_E_UNSUPPORTED;
         p.err_text = "no render kernel for this scene and tuning";
-        return p;
     }
+}
+
+template <typename R>
+RenderPlan plan_render(const RenderKnobs& k, const DevScene<R>& sc, const rtw_camera& cam, uint32_t n_local_tiles,
+                       uint32_t chunk, const SceneScale& scale) {
+    RenderPlan p;
+    const uint32_t spp = cam.samples_per_pixel;
+    p.chunk = chunk;
+    p.n_chunks = spp ? (spp + chunk - 1) / chunk : 0;
+    uint32_t group = k.group;
+    if (group == 0) {
+        // Persistent waves (default) have no per-task drain; a task boundary
+        // mixes two tiles' items in the wave (less coherent), the launch's tail
+        // grows with the task size.  Longest tiles first leaves cheap tiles
+        // for the end, so ~2^17 tasks (~32 per resident wave): C2 split over
+        // 1 / 2 / 4 / 8 ranks -> 32 / 28 / 15 / 8 chunks per task (N = 1:
+        // group 32 93.7 ms vs 16 94.4, 4 104.4; an 8-way share: 8 13.2 ms vs
+        // 4 13.6).  One task per wave instead pays a drain per task: ~2^17.
+        constexpr uint32_t kMinAutoGroup = 4, kMaxAutoGroup = 32;
+        const uint64_t target = k.target_tasks ? k.target_tasks : kAutoTasks;
+        const uint64_t n_groups = n_local_tiles ? (target + n_local_tiles - 1) / n_local_tiles : 1;
+        group = (uint32_t)((p.n_chunks + n_groups - 1) / std::max<uint64_t>(n_groups, 1));
+        group = std::max(kMinAutoGroup, std::min(group, kMaxAutoGroup));
+    }
+    // at most 4096 chunks per task: the kernel divides item indices q < 64 * group
+    // by the group with a multiply-high by ceil(2^32 / group), exact while 64 group^2 < 2^32
+    p.group = std::max<uint32_t>(1, std::min<uint32_t>(std::min<uint32_t>(group, 4096u), std::max<uint32_t>(p.n_chunks, 1)));
+    p.n_groups = p.n_chunks ? (p.n_chunks + p.group - 1) / p.group : 0;
+    p.n_tasks = n_local_tiles * p.n_groups;
+    plan_world<R>(k, sc, cam.center, scale, p);
+    if (p.err) return p;
     // auto: walks that cross the whole grid in few pieces give the wave little to
     // share, short ones pay each piece's setup: f32, a fourteenth of the grid's
     // widest side, 4..16 cells (at the default 1/2 cell per light: C3, ~16 cells
@@ -239,6 +248,10 @@ template uint32_t plan_chunk<float>(const RenderKnobs&, uint32_t, uint32_t, size
 template uint32_t plan_chunk<double>(const RenderKnobs&, uint32_t, uint32_t, size_t);
 template WindowPlan plan_windows<float>(const RenderKnobs&, uint32_t, uint32_t, size_t);
 template WindowPlan plan_windows<double>(const RenderKnobs&, uint32_t, uint32_t, size_t);
+template void plan_world<float>(const RenderKnobs&, const DevScene<float>&, const double*, const SceneScale&,
+                                RenderPlan&);
+template void plan_world<double>(const RenderKnobs&, const DevScene<double>&, const double*, const SceneScale&,
+                                 RenderPlan&);
 template RenderPlan plan_render<float>(const RenderKnobs&, const DevScene<float>&, const rtw_camera&, uint32_t,
                                        uint32_t, const SceneScale&);
 template RenderPlan plan_render<double>(const RenderKnobs&, const DevScene<double>&, const rtw_camera&, uint32_t,

@@ -137,6 +137,13 @@ struct WindowPlan {
 template <typename R>
 WindowPlan plan_windows(const RenderKnobs& k, uint32_t spp, uint32_t n_local_tiles, size_t dev_total);
 
+// The world decision of step 2, shared with the ray queries (query_plan.hpp):
+// fills p.accel, world, opts, bvh_width, stack, launch_lds, light_bvh, hit64,
+// robust (by the scene's scale as seen from `center`) and err / err_text.
+template <typename R>
+void plan_world(const RenderKnobs& k, const DevScene<R>& sc, const double center[3], const SceneScale& scale,
+                RenderPlan& p);
+
 // Step 2: everything else, for the chunk that was actually allocated.
 template <typename R>
 RenderPlan plan_render(const RenderKnobs& k, const DevScene<R>& sc, const rtw_camera& cam, uint32_t n_local_tiles,

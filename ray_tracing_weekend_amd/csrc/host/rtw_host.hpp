@@ -260,6 +260,26 @@ class Camera {
     rtw_camera c_;
 };
 
+// Batched ray queries (rtw_hit_rays / rtw_light_pdf_rays, include/rtw.h), f64
+// on one device; defined in host/ray_queries.cpp.  rays: 6 values per ray
+// {origin, direction}.
+struct RayHit {                       // HitRecord::new, hittable.rs:100-129
+    double t;
+    Point3 p;
+    Vec3 normal;                      // against the ray (front-face adjusted)
+    double u, v;
+    int32_t object;                   // planes, quads, cuboids, spheres, each in list order; -1: a miss
+    int32_t material;                 // index into FlatScene::mat_type
+    bool front_face;
+    int32_t kind;                     // RTW_PRIM_*
+};
+// world.hit(&r, t_min..=INFINITY) per ray (a miss: object -1, everything else 0)
+std::vector<RayHit> hit_rays(const HittableList& world, const HittableList& lights, const std::vector<double>& rays,
+                             double t_min = 2.220446049250313e-16, const RenderOptions& opt = {});
+// lights.pdf_value(origin, direction) per ray (hittable_list.rs:408-412)
+std::vector<double> light_pdf(const HittableList& world, const HittableList& lights, const std::vector<double>& rays,
+                              const RenderOptions& opt = {});
+
 namespace scenes {
 // scenes::simple restated with the build's seeded RNG; grid a, b in [-n, n).
 std::tuple<HittableList, HittableList, CameraBuilder> simple(uint64_t seed, int n = 11);
