@@ -602,6 +602,62 @@ typedef struct rtw_query_stats {
 /* Counters of the last query (waits for it); RTW_E_INVALID before the first. */
 int rtw_get_query_stats(rtw_ctx *ctx, rtw_query_stats *stats);
 
+/* ---- feature buffers for denoisers: first-hit albedo, normal, distance ----
+ * One fused pass over the render's own primary rays.  For pixel (i, j) and the
+ * absolute sample index s it takes the ray of Camera::get_ray (camera.rs:274-
+ * 293) -- the ray a render traces for that (seed, pixel, sample): the same
+ * stream, the same draws, defocus included -- and its world.hit(&r,
+ * f64::EPSILON..=INFINITY).  Each sample contributes 8 channels:
+ *   0-2 albedo    hit: by material -- Lambertian its texture's get_colour(u, v,
+ *                 p), Metal its albedo, Dielectric (1, 1, 1), DiffuseLight its
+ *                 texture's colour (the emitted colour: may exceed 1),
+ *                 Invisible (0, 0, 0); miss: the camera's background
+ *   3-5 normal    hit: the HitRecord normal, front-face adjusted, as
+ *                 rtw_hit_rays reports it (a cuboid's in object space); miss: 0
+ *   6   distance  hit: t * sqrt((dx dx + dy dy) + dz dz), each operation
+ *                 rounded by itself; miss: 0
+ *   7   hits      hit: 1; miss: 0
+ * features[(j * W + i) * 8 + c] is the sequential f64 fold ((acc + f_s0) +
+ * f_s0+1) + ... over the pixel's samples in increasing s: sums, not means, as
+ * every image here; j = 0 is the bottom row.  The sums are f64 in both
+ * precisions: RTW_F64 computes each sample in the reference's f64 arithmetic,
+ * RTW_F32 in the plain f32 arithmetic of a query, widened exactly.
+ *
+ * Pixel p folds the samples [first_sample, min(first_sample + n_samples,
+ * counts[p])) -- all of [first_sample, first_sample + n_samples) when counts
+ * is NULL -- onto features, which is read when first_sample > 0 and defined by
+ * the call when it is 0 (a pixel without samples: zeros).  So windows compose
+ * bit for bit, and rtw_render_adaptive's counts with first_sample 0 and
+ * n_samples = max_samples give the features of exactly the samples each
+ * pixel's colour was made of.  cam->samples_per_pixel and max_depth are not
+ * read.  n_samples = 0 does nothing.
+ * ids (may be NULL): H*W*2 int32 {object id or -1, material id (0 on a miss)}
+ * of each pixel's sample 0; written only by a call with first_sample == 0, for
+ * the pixels that take a sample, and left untouched otherwise.
+ *
+ * The pass runs the traversal a render of the scene would run under the same
+ * tuning keys (as the ray queries) on its own buffers: a render or a query
+ * before and after it is unchanged.  It fills the query stats
+ * (rtw_get_query_stats): rays = samples traced, hits, node_visits,
+ * sphere_tests, kernel = the world that ran, is_light_pdf = 0, kernel_ms.
+ * A plane whose UV is not finite (the reference panics) is handled as
+ * rtw_hit_rays handles it: the NaN reaches the texture.
+ *
+ * Errors: RTW_E_INVALID -- before any device call -- for a NULL context,
+ * camera or features, a buffer that is too small or (device form) features
+ * not 16-byte aligned, first_sample + n_samples beyond 2^32 - 1, a width or
+ * height of 2^16 or more; RTW_E_NO_SCENE before rtw_set_scene;
+ * RTW_E_UNSUPPORTED on a multi-device or virtual-rank context.  The host form
+ * is synchronous; the device form enqueues on `stream` as rtw_render_device
+ * does (NULL: the context's own, RTW_STREAM_NULL: the null stream) and never
+ * waits for the device. */
+int rtw_render_features(rtw_ctx *ctx, const rtw_camera *cam, uint64_t seed, uint32_t first_sample,
+                        uint32_t n_samples, const uint32_t *counts, double *features, int32_t *ids);
+int rtw_render_features_device(rtw_ctx *ctx, const rtw_camera *cam, uint64_t seed, uint32_t first_sample,
+                               uint32_t n_samples, const uint32_t *d_counts, size_t counts_bytes,
+                               double *d_features, size_t features_bytes, int32_t *d_ids, size_t ids_bytes,
+                               void *stream);
+
 /* ---- scenes::simple (scenes/src/lib.rs:155-233) ----------------------- */
 /* The library owns the arrays; view them through rtw_world_scene(). grid_n =
  * 11 is the reference scene; larger n gives the synthetic C3/C5 fields. */

@@ -32,7 +32,7 @@ __all__ = [
     "Quad", "Cuboid", "Transformation", "translation", "rotation", "SolidColour", "CheckerTexture",
     "NoiseTexture", "Perlin", "HittableList", "BoundedVolumeHierarchy", "SceneSoA", "flatten",
     "CameraBuilder", "Camera", "Renderer", "scenes", "encode_rgb8", "write_ppm", "RenderError",
-    "RTW_F32", "RTW_F64",
+    "RTW_F32", "RTW_F64", "feature_means",
 ]
 
 _lib = _capi.load()   # raises if librtw.so is missing: there is no CPU fallback
@@ -538,6 +538,17 @@ class Camera:
             r.set_scene(flatten(world, lights))
             return r.render_adaptive(self, seed, min_samples, max_samples, window, tolerance)
 
+    def render_features(self, world, lights, first: int = 0, n: int | None = None, *, seed: int = 0x5EED0001,
+                        counts=None, want_ids: bool = True, precision: int = RTW_F64, device: int = 0,
+                        accel: int = RTW_ACCEL_AUTO):
+        """The denoising guides of this camera's render of the scene
+        (Renderer.render_features): (features [H, W, 8], ids [H, W, 2] | None),
+        with the scene staged for this one call."""
+        with Renderer(device=device, precision=precision) as r:
+            r.set_accel(accel)
+            r.set_scene(flatten(world, lights))
+            return r.render_features(self, seed, first, n, counts=counts, want_ids=want_ids)
+
 
 class Renderer:
     """An rtw_ctx: a device (or, with `devices`, one rank per listed GPU:
@@ -868,6 +879,71 @@ class Renderer:
                                             pdf.ctypes.data_as(C.c_void_p)), "rtw_light_pdf_rays")
         return pdf
 
+    # ---- feature buffers for denoisers (rtw_render_features)
+    def render_features(self, cam: Camera, seed: int, first: int = 0, n: int | None = None, *, counts=None,
+                        features=None, want_ids: bool = True):
+        """First-hit guides of the render's own primary rays: (features
+        [H, W, 8] float64 sums {albedo rgb, normal xyz, distance, hits}, ids
+        [H, W, 2] int32 {object id or -1, material id} of each pixel's sample 0,
+        or None).  Pixel p folds the samples [first, min(first + n,
+        counts[p])) in order onto `features` (zeros when None; n defaults to
+        cam.samples_per_pixel - first), so windows and counts compose bit for
+        bit with a one-shot pass, and render_adaptive's counts with n =
+        max_samples give the guides of exactly the samples each colour was
+        made of.  The ids are written by a call with first == 0 only (None
+        when first > 0 or want_ids is false).  Sums, not means: see
+        feature_means.  numpy arrays (or None) go through the host entry; with
+        a torch GPU tensor as `features` or `counts` the call goes through the
+        device entry on torch's current stream, without a host copy, `features`
+        is updated in place and torch tensors come back.  rtw_get_query_stats
+        then holds the pass's counters."""
+        H, W = cam.raw.image_height, cam.raw.image_width
+        first = int(first)
+        n = max(int(cam.raw.samples_per_pixel) - first, 0) if n is None else int(n)
+        with_ids = bool(want_ids) and first == 0
+        is_torch = [type(a).__module__.split(".")[0] == "torch" for a in (features, counts)]
+        if any(is_torch):
+            import torch
+            dev = torch.device("cuda", self.device)
+            for a, t, dt, shape, what in ((features, is_torch[0], torch.float64, (H, W, 8), "features"),
+                                          (counts, is_torch[1], torch.int32, (H, W), "counts")):
+                if a is None:
+                    continue
+                ok_dt = t and (a.dtype == dt or (what == "counts" and a.dtype == getattr(torch, "uint32", dt)))
+                if not (ok_dt and a.is_cuda and a.device.index == self.device and a.is_contiguous()
+                        and tuple(a.shape) == shape):
+                    raise RenderError(_capi.RTW_E_INVALID, f"render_features: {what} must be a contiguous "
+                                      f"{list(shape)} {dt} tensor on device {self.device}")
+            if features is None:
+                features = torch.zeros((H, W, 8), dtype=torch.float64, device=dev)
+            ids = torch.zeros((H, W, 2), dtype=torch.int32, device=dev) if with_ids else None
+            stream = _torch_stream(self.device)
+            self._check(_lib.rtw_render_features_device(
+                self.ctx, C.byref(cam.raw), C.c_uint64(seed), first, n,
+                C.c_void_p(counts.data_ptr()) if counts is not None else None,
+                counts.numel() * 4 if counts is not None else 0,
+                C.c_void_p(features.data_ptr()), features.numel() * 8,
+                C.c_void_p(ids.data_ptr()) if ids is not None else None, ids.numel() * 4 if ids is not None else 0,
+                C.c_void_p(stream) if stream else None), "rtw_render_features_device")
+            return features, ids
+        if features is None:
+            features = np.zeros((H, W, 8), np.float64)
+        elif not (isinstance(features, np.ndarray) and features.dtype == np.float64 and features.shape == (H, W, 8)
+                  and features.flags.c_contiguous and features.flags.writeable):
+            raise RenderError(_capi.RTW_E_INVALID, f"render_features: features must be a C-contiguous float64 "
+                              f"array of shape {(H, W, 8)}")
+        cnt = None
+        if counts is not None:
+            cnt = np.ascontiguousarray(np.asarray(counts, np.uint32))
+            if cnt.shape != (H, W):
+                raise RenderError(_capi.RTW_E_INVALID, f"render_features: counts must have shape {(H, W)}")
+        ids = np.zeros((H, W, 2), np.int32) if with_ids else None
+        self._check(_lib.rtw_render_features(
+            self.ctx, C.byref(cam.raw), C.c_uint64(seed), first, n,
+            cnt.ctypes.data_as(C.c_void_p) if cnt is not None else None, features.ctypes.data_as(C.c_void_p),
+            ids.ctypes.data_as(C.c_void_p) if ids is not None else None), "rtw_render_features")
+        return features, ids
+
     def get_query_stats(self) -> "_capi.rtw_query_stats":
         """Counters of the last query (rtw_get_query_stats): rays, hits, node
         visits, sphere tests, light tests, the world / light path that ran."""
@@ -1069,3 +1145,25 @@ def write_ppm(path: str, sums: np.ndarray, spp) -> int:
     if n < 0:
         raise RenderError(n, f"cannot write {path}")
     return n
+
+
+def feature_means(features, n):
+    """The guides a denoiser reads from render_features' sums [H, W, 8], for
+    the sample count n (a number, or the [H, W] counts the pass was given):
+    (albedo [H, W, 3] = sums / n, normal [H, W, 3] = the normal sum normalised
+    (0 where no sample hit), distance [H, W] = sum / hits (inf where no sample
+    hit), coverage [H, W] = hits / n).  A pixel with n = 0 has albedo and
+    coverage 0.  Pure numpy."""
+    f = np.asarray(features, np.float64)
+    if f.ndim != 3 or f.shape[2] != 8:
+        raise RenderError(_capi.RTW_E_INVALID, f"features must be [H, W, 8], got {list(f.shape)}")
+    cnt = np.broadcast_to(np.asarray(n, np.float64), f.shape[:2])
+    hits = f[..., 7]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        sampled = cnt > 0
+        albedo = np.where(sampled[..., None], f[..., 0:3] / cnt[..., None], 0.0)
+        coverage = np.where(sampled, hits / cnt, 0.0)
+        length = np.sqrt((f[..., 3:6] ** 2).sum(-1))
+        normal = np.where((length > 0)[..., None], f[..., 3:6] / length[..., None], 0.0)
+        distance = np.where(hits > 0, f[..., 6] / hits, np.inf)
+    return albedo, normal, distance, coverage

@@ -155,6 +155,11 @@ PROTOTYPES = [
     ("rtw_light_pdf_rays_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t,
                                             C.c_void_p]),
     ("rtw_get_query_stats", C.c_int, [C.c_void_p, C.POINTER(rtw_query_stats)]),
+    ("rtw_render_features", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32, C.c_uint32,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rtw_render_features_device", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32, C.c_uint32,
+                                             C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                             C.c_size_t, C.c_void_p]),
     ("rtw_scene_simple", C.c_void_p, [C.c_uint64, C.c_int]),
     ("rtw_world_scene", C.POINTER(rtw_scene), [C.c_void_p]),
     ("rtw_world_camera_builder", None, [C.c_void_p, C.POINTER(rtw_camera_builder)]),

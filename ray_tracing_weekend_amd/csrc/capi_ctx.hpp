@@ -1,6 +1,7 @@
 // capi_ctx.hpp -- private to the C-ABI units (capi.cpp, capi_render.cpp,
-// capi_lpt.cpp, capi_adaptive.cpp, capi_multi.cpp, capi_query.cpp): the context behind
-// include/rtw.h's rtw_ctx and the helpers they share.
+// capi_lpt.cpp, capi_adaptive.cpp, capi_multi.cpp, capi_query.cpp,
+// capi_features.cpp): the context behind include/rtw.h's rtw_ctx and the
+// helpers they share.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -67,6 +68,30 @@ struct SplitState {
     void local_tiles(uint32_t w, uint32_t h, uint32_t r, uint32_t nranks, std::vector<uint32_t>& out) const {
         rtw::local_tiles(active(w, h, nranks) ? &rank : nullptr, w, h, r, nranks, out);
     }
+};
+
+// Batched ray queries (capi_query.cpp) and the feature pass (capi_features.cpp):
+// their counters, events and staging buffers, allocated by the first of them.
+struct QueryState {
+    // rtw::kQueryCounters counters, then the feature pass's next tile (kFeatureNextTile)
+    unsigned long long* d_counters = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // the queries' host forms' staging: rays in, records out
+    void* d_rays = nullptr;
+    size_t rays_cap = 0;
+    void* d_out = nullptr;
+    size_t out_cap = 0;
+    void* d_ids = nullptr;
+    size_t ids_cap = 0;
+    // rtw_render_features' staging: the sums, the counts, the ids
+    void* d_feat = nullptr;
+    size_t feat_cap = 0;
+    void* d_feat_counts = nullptr;
+    size_t feat_counts_cap = 0;
+    void* d_feat_ids = nullptr;
+    size_t feat_ids_cap = 0;
+    rtw_query_stats last{};
+    bool any = false;                 // a query was launched
 };
 
 struct rtw_ctx {
@@ -141,9 +166,9 @@ struct rtw_ctx {
     uint32_t stats_ranks = 1;
     // the last multi-device render gave this rank no tile: its stats are those of no work
     bool no_work = false;
-    // batched ray queries (capi_query.cpp): their own buffers, counters and events,
-    // allocated by the first query -- nothing of the render's is touched
-    struct QueryState* query = nullptr;
+    // batched ray queries and the feature pass: their own buffers, counters and events,
+    // allocated by the first of them -- nothing of the render's is touched
+    QueryState* query = nullptr;
 };
 
 static inline int fail(rtw_ctx* c, int code, const std::string& msg) {
@@ -258,3 +283,5 @@ int gather_done(rtw_ctx* c, hipStream_t s0);
 void destroy_ranks(rtw_ctx* c);
 // capi_query.cpp: rtw_destroy's part for the query state (the context's device is current)
 void destroy_query(rtw_ctx* c);
+// capi_query.cpp: the context's query state, allocated on first use
+int query_state(rtw_ctx* c);

@@ -10,20 +10,6 @@
 #include "capi_ctx.hpp"
 #include "host/query_plan.hpp"
 
-struct QueryState {
-    unsigned long long* d_counters = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // the host forms' staging: rays in, records out
-    void* d_rays = nullptr;
-    size_t rays_cap = 0;
-    void* d_out = nullptr;
-    size_t out_cap = 0;
-    void* d_ids = nullptr;
-    size_t ids_cap = 0;
-    rtw_query_stats last{};
-    bool any = false;                 // a query was launched
-};
-
 void destroy_query(rtw_ctx* c) {
     QueryState* q = c->query;
     if (!q) return;
@@ -31,24 +17,29 @@ void destroy_query(rtw_ctx* c) {
     if (q->d_rays) (void)hipFree(q->d_rays);
     if (q->d_out) (void)hipFree(q->d_out);
     if (q->d_ids) (void)hipFree(q->d_ids);
+    if (q->d_feat) (void)hipFree(q->d_feat);
+    if (q->d_feat_counts) (void)hipFree(q->d_feat_counts);
+    if (q->d_feat_ids) (void)hipFree(q->d_feat_ids);
     if (q->ev0) (void)hipEventDestroy(q->ev0);
     if (q->ev1) (void)hipEventDestroy(q->ev1);
     delete q;
     c->query = nullptr;
 }
 
-namespace {
-
 int query_state(rtw_ctx* c) {
     if (c->query) return RTW_OK;
     QueryState* q = new (std::nothrow) QueryState();
     if (!q) return fail(c, RTW_E_DEVICE, "out of memory");
     c->query = q;
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&q->d_counters), rtw::kQueryCounters * sizeof(unsigned long long)));
+    // (one more word than the queries count in: the feature pass's tile counter)
+    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&q->d_counters),
+                         (rtw::kQueryCounters + 1) * sizeof(unsigned long long)));
     HIP_TRY(c, hipEventCreate(&q->ev0));
     HIP_TRY(c, hipEventCreate(&q->ev1));
     return RTW_OK;
 }
+
+namespace {
 
 // what both queries refuse before anything else; RTW_OK: the context can run one
 int query_checks(rtw_ctx* c, const void* rays, uint64_t n) {

@@ -4,6 +4,12 @@
 // writes image.ppm (P3, rows top to bottom).
 //
 //   rtw <scene> [--debug] [--seed N] [--f64] [--device N | --device-mask M] [--config PATH] [--out PATH]
+//       [--features PREFIX]
+//
+// --features PREFIX also writes the denoising guides of the render
+// (rtw_render_features, on one device): PREFIX_albedo.ppm, the albedo sums with
+// the sample count, and PREFIX_normal.ppm, (mean normal + 1) / 2 -- squared
+// before the writer's sqrt, so that the displayed value is linear.
 //
 // <scene> is one of clap's ValueEnum names of main.rs:29-38 (cornell-box,
 // debug, checkered-spheres, perlin-spheres, plane, simple, simple-light,
@@ -53,7 +59,7 @@ bool read_config(const std::string& path, std::map<std::string, std::string>* kv
 }  // namespace
 
 int main(int argc, char** argv) {
-    std::string scene, config = "Config.toml", out = "image.ppm";
+    std::string scene, config = "Config.toml", out = "image.ppm", features;
     rtw::RenderOptions opt;
     for (int a = 1; a < argc; ++a) {
         std::string s = argv[a];
@@ -65,6 +71,7 @@ int main(int argc, char** argv) {
         else if (s == "--device-mask" && a + 1 < argc) opt.device_mask = strtoull(argv[++a], nullptr, 0);
         else if (s == "--config" && a + 1 < argc) config = argv[++a];
         else if (s == "--out" && a + 1 < argc) out = argv[++a];
+        else if (s == "--features" && a + 1 < argc) features = argv[++a];
         else if (scene.empty()) scene = s;
         else { fprintf(stderr, "unexpected argument %s\n", s.c_str()); return 2; }
     }
@@ -128,6 +135,27 @@ int main(int argc, char** argv) {
         if (rtw_write_ppm(out.c_str(), sums.data(), W, H, spp) < 0) {
             fprintf(stderr, "cannot write %s\n", out.c_str());
             return 1;
+        }
+        if (!features.empty()) {
+            rtw::RenderOptions fopt = opt;
+            fopt.device_mask = 0;   // the feature pass runs on one device
+            const std::vector<double> f = cam.render_features(world, lights, 0, spp, {}, nullptr, fopt);
+            std::vector<double> albedo((size_t)W * H * 3), normal((size_t)W * H * 3);
+            for (size_t px = 0; px < (size_t)W * H; ++px) {
+                const double* v = &f[px * 8];
+                const double len = sqrt((v[3] * v[3] + v[4] * v[4]) + v[5] * v[5]);
+                for (int c = 0; c < 3; ++c) {
+                    albedo[px * 3 + c] = v[c];
+                    const double shown = ((len > 0.0 ? v[3 + c] / len : 0.0) + 1.0) / 2.0;
+                    normal[px * 3 + c] = shown * shown;
+                }
+            }
+            const std::string fa = features + "_albedo.ppm", fn = features + "_normal.ppm";
+            if (rtw_write_ppm(fa.c_str(), albedo.data(), W, H, spp) < 0 ||
+                rtw_write_ppm(fn.c_str(), normal.data(), W, H, 1) < 0) {
+                fprintf(stderr, "cannot write %s / %s\n", fa.c_str(), fn.c_str());
+                return 1;
+            }
         }
     } catch (const rtw::Error& e) {
         fprintf(stderr, "rtw: %s (code %d)\n", e.what(), e.code());

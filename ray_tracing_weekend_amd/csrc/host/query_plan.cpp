@@ -6,11 +6,11 @@
 namespace rtw {
 
 template <typename R>
-QueryPlan plan_query(const RenderKnobs& k, const DevScene<R>& sc, const SceneScale& scale) {
+QueryPlan plan_query(const RenderKnobs& k, const DevScene<R>& sc, const SceneScale& scale, const double* center) {
     QueryPlan q;
     RenderPlan p;
     const double origin[3] = {0.0, 0.0, 0.0};
-    plan_world<R>(k, sc, origin, scale, p);
+    plan_world<R>(k, sc, center ? center : origin, scale, p);
     q.accel = p.accel;
     q.world = p.world;
     q.robust = sizeof(R) == 4 ? p.robust : 0u;
@@ -43,7 +43,7 @@ QueryPlan plan_query(const RenderKnobs& k, const DevScene<R>& sc, const SceneSca
     return q;
 }
 
-template QueryPlan plan_query<float>(const RenderKnobs&, const DevScene<float>&, const SceneScale&);
-template QueryPlan plan_query<double>(const RenderKnobs&, const DevScene<double>&, const SceneScale&);
+template QueryPlan plan_query<float>(const RenderKnobs&, const DevScene<float>&, const SceneScale&, const double*);
+template QueryPlan plan_query<double>(const RenderKnobs&, const DevScene<double>&, const SceneScale&, const double*);
 
 }  // namespace rtw

@@ -24,8 +24,11 @@ struct QueryPlan {
     const char* err_text = "";
 };
 
-// A query has no camera: knob robust = 2 judges the scene's scale from the origin.
+// A query has no camera: knob robust = 2 judges the scene's scale from the origin
+// (center null).  The feature pass (rtw_render_features) traces a camera's primary
+// rays with the query's plan: it passes the camera's center, as a render plan does.
 template <typename R>
-QueryPlan plan_query(const RenderKnobs& k, const DevScene<R>& sc, const SceneScale& scale);
+QueryPlan plan_query(const RenderKnobs& k, const DevScene<R>& sc, const SceneScale& scale,
+                     const double* center = nullptr);
 
 }  // namespace rtw

@@ -254,6 +254,16 @@ class Camera {
                                                             uint32_t min_samples, uint32_t max_samples,
                                                             uint32_t window, double tolerance,
                                                             const RenderOptions& opt = {}) const;
+    // Denoising guides of this camera's render (rtw_render_features, include/rtw.h;
+    // one device): per pixel the f64 sums of {albedo rgb, normal xyz, distance, hits}
+    // over the primary rays of the samples [first, min(first + n, counts[p])) --
+    // counts empty: all of them; n 0: samples_per_pixel - first -- in image order
+    // [H][W][8], j = 0 the bottom row.  ids (may be null) receives [H][W][2]
+    // {object or -1, material} of each pixel's sample 0 when first is 0.  Defined in
+    // host/render_features.cpp.
+    std::vector<double> render_features(const HittableList& world, const HittableList& lights, uint32_t first = 0,
+                                        uint32_t n = 0, const std::vector<uint32_t>& counts = {},
+                                        std::vector<int32_t>* ids = nullptr, const RenderOptions& opt = {}) const;
     const rtw_camera& raw() const { return c_; }
 
    private:
