@@ -513,8 +513,23 @@ int rtw_get_split(rtw_ctx *ctx, uint32_t image_width, uint32_t image_height, uin
  * such count.  With tuning "balance" (1, the default) a multi-device
  * context deals its split from these costs by itself: the first
  * rtw_render_image_device of a camera counts, the second deals and renders
- * balanced (re-dealt when the scene or camera changes). */
+ * balanced (re-dealt when the scene or camera changes).  A provably empty
+ * tile (rtw_culled_tiles) is never traced and gets no task: it is reported
+ * with the smallest cost, 1 (the fold answers it; 0 stays "not counted"),
+ * which rtw_split_deal deals like any other cost. */
 int rtw_tile_costs(rtw_ctx *ctx, const rtw_camera *cam, uint32_t rank, uint32_t nranks, uint32_t *tile_cost);
+/* Provably empty tiles (RTW_F64, scenes of spheres and planes only; tuning
+ * "tile_cull", default 1, 0 = off): a tile whose every camera ray -- every
+ * lens point, every pixel offset -- misses every primitive by a margin that
+ * dominates the rounding of the reference's tests is not traced.  Every
+ * sample of it is the background, and the fold adds that constant in the
+ * reference's order, so the image is the same bit for bit; stats.samples and
+ * stats.segments count its samples (one segment each).  Nothing is culled in
+ * RTW_F32, in adaptive renders, for scenes with quads, cuboids, textures or
+ * emitters, or when a scene or camera value is not finite or beyond 2^130.
+ * Returns the number of such tiles in the last render (summed over the ranks
+ * of a multi-device render); 0 for a NULL context. */
+uint32_t rtw_culled_tiles(rtw_ctx *ctx);
 /* Counters of the last render (waits for it to finish).  Returns
  * RTW_E_NO_LIGHTS / RTW_E_PANIC (stats still filled) when a sample reached a
  * reference panic, RTW_E_INVALID before the first render.  A multi-device

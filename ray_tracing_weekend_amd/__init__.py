@@ -791,6 +791,11 @@ class Renderer:
                     "rtw_tile_costs")
         return out
 
+    def culled_tiles(self) -> int:
+        """Tiles of the last render that were provably empty and answered by
+        the fold without tracing (rtw_culled_tiles; tuning "tile_cull")."""
+        return int(_lib.rtw_culled_tiles(self.ctx))
+
     def get_timings(self, n: int = 64):
         """(render_ms, total_ms) lists for the last n renders (HIP events)."""
         a, b = (C.c_float * n)(), (C.c_float * n)()

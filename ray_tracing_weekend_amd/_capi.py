@@ -144,6 +144,7 @@ PROTOTYPES = [
     ("rtw_set_split", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p]),
     ("rtw_get_split", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p]),
     ("rtw_tile_costs", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint32, C.c_uint32, _u32p]),
+    ("rtw_culled_tiles", C.c_uint32, [C.c_void_p]),
     ("rtw_get_stats", C.c_int, [C.c_void_p, C.POINTER(rtw_stats)]),
     ("rtw_get_stats_rank", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(rtw_stats)]),
     ("rtw_get_timings", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]),

@@ -56,6 +56,8 @@ void rtw_destroy(rtw_ctx* c) {
     if (c->d_counters) (void)hipFree(c->d_counters);
     if (c->lpt.d_cost) (void)hipFree(c->lpt.d_cost);
     if (c->lpt.d_tasks) (void)hipFree(c->lpt.d_tasks);
+    if (c->cull.d_flags) (void)hipFree(c->cull.d_flags);
+    if (c->cull.d_tasks) (void)hipFree(c->cull.d_tasks);
     if (c->split.d_tile_map) (void)hipFree(c->split.d_tile_map);
     if (c->split.d_tile_slot) (void)hipFree(c->split.d_tile_slot);
     if (c->lpt.ev) (void)hipEventDestroy(c->lpt.ev);
@@ -115,6 +117,7 @@ int rtw_set_tuning(rtw_ctx* c, const char* key, int64_t value) {
     else if (k == "auto_accel") t.auto_accel = (int)std::min<int64_t>(value, RTW_ACCEL_BVH);
     else if (k == "balance") t.balance = value ? 1u : 0u;
     else if (k == "cost_time") t.cost_time = value ? 1u : 0u;
+    else if (k == "tile_cull") t.tile_cull = value ? 1u : 0u;
     else if (k == "guide_div") { t.guide_div = (uint32_t)std::min<int64_t>(value, 1 << 24); c->lpt.st.tab_valid = false; }
     else if (k == "guide_max") { t.guide_max = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 1), 4095); c->lpt.st.tab_valid = false; }
     else if (k == "guide_floor") { t.guide_floor = std::max<uint64_t>(1, (uint64_t)value); c->lpt.st.tab_valid = false; }
@@ -194,13 +197,19 @@ int rtw_set_scene(rtw_ctx* c, const rtw_scene* s) {
     const uint32_t light_leaf = t.light_leaf ? t.light_leaf : rtw::kLeafMax;
     // the light grid only for light lists long enough to skip the linear loop
     const double grid = s->n_lights >= t.light_bvh_min ? t.light_grid / 16.0 : 0.0;
+    // f64: the classifier of provably empty tiles keeps the scene's values and the staged tree
+    std::shared_ptr<rtw::CullScene> cs;
+    if (c->precision == RTW_F64) cs = std::make_shared<rtw::CullScene>();
     std::vector<unsigned char> blob = c->precision == RTW_F32
                                           ? rtw::stage_scene<float>(s, &tmp32, 0, leaf, light_leaf, grid)
-                                          : rtw::stage_scene<double>(s, &tmp64, 0, leaf, light_leaf, grid);
+                                          : rtw::stage_scene<double>(s, &tmp64, 0, leaf, light_leaf, grid, &cs->bvh);
+    if (cs) rtw::cull_scene_init(s, cs.get());
     const rtw::SceneScale scale = c->precision == RTW_F32 ? rtw::scene_scale(s, tmp32) : rtw::scene_scale(s, tmp64);
     for (uint32_t k = 0; k < rtw_device_count(c); ++k) {   // multi-device: the same scene on every rank
         rtw_ctx* ck = rtw_device_ctx(c, k);
         rc = upload_scene(ck, blob, tmp32, tmp64, scale);
+        ck->cull_scene = cs;
+        ck->cull.st.drop();
         if (rc) {
             // no rank keeps a scene: a partial update must not render one image
             // from tiles of two scenes
@@ -267,6 +276,16 @@ int rtw_get_split(rtw_ctx* c, uint32_t W, uint32_t H, uint32_t nranks, uint32_t*
     return c->split.automatic ? 2 : 1;
 }
 
+uint32_t rtw_culled_tiles(rtw_ctx* c) {
+    if (!c) return 0;
+    uint32_t n = 0;
+    for (uint32_t k = 0; k < std::min(std::max(c->stats_ranks, 1u), rtw_device_count(c)); ++k) {
+        const rtw_ctx* ck = rtw_device_ctx(c, k);
+        if (ck && !ck->no_work) n += ck->last_culled;
+    }
+    return n;
+}
+
 int rtw_last_kernel(const rtw_ctx* c) {
     if (!c) return RTW_E_INVALID;
     return c->last_variant & 0xffff;
@@ -297,7 +316,7 @@ int get_stats_one(rtw_ctx* c, rtw_stats* out) {
     HIP_TRY(c, hipMemcpy(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost));
     float ms = 0.f;
     HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    c->last.segments = h[0];
+    c->last.segments = h[0] + c->cull_segments;   // (a culled sample: one segment that misses)
     c->last.lambertian = h[1];
     c->last.node_visits = h[2];
     // the brute-force sweep tests every sphere on every segment

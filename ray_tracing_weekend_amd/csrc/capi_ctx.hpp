@@ -10,6 +10,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -18,6 +19,7 @@
 #include "host/render_pass.hpp"
 #include "host/render_plan.hpp"
 #include "host/stage_scene.hpp"
+#include "host/tile_cull.hpp"
 #include "host/tiles.hpp"
 #include "rtw_kernels.h"
 
@@ -31,6 +33,16 @@ struct LptCache {
     size_t cost_cap = 0;
     hipEvent_t ev = nullptr;          // after the last counting render (st.pending)
     void* d_tasks = nullptr;          // the task list st.h_tasks
+    size_t tasks_cap = 0;
+};
+
+// Provably empty tiles (host/tile_cull.hpp): the flags of the last classified key
+// and their plain-order task list, with their device copies (capi_render.cpp)
+struct CullCache {
+    rtw::CullState st;
+    void* d_flags = nullptr;          // st.flags
+    size_t flags_cap = 0;
+    void* d_tasks = nullptr;          // st.h_tasks
     size_t tasks_cap = 0;
 };
 
@@ -136,6 +148,11 @@ struct rtw_ctx {
     unsigned long long* d_counters = nullptr;
     std::vector<unsigned char> h_out;
     LptCache lpt;
+    // f64 contexts: what the tile classifier reads of the staged scene (shared by the ranks)
+    std::shared_ptr<const rtw::CullScene> cull_scene;
+    CullCache cull;
+    uint32_t last_culled = 0;         // provably empty tiles of the last render (rtw_culled_tiles)
+    uint64_t cull_segments = 0;       // ... their samples so far, one segment each (stats.segments)
     SplitState split;
     rtw_stats last{};
     int last_variant = 0;             // render kernel of the last render: rtw_kernels.h variant_code
@@ -261,9 +278,11 @@ int render_pass(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t rank,
                 hipStream_t stream, const rtw::Pass& pass);
 // capi_lpt.cpp: the task order of a render of `key` (the plan says longest tiles first
 // applies) -- with costs, p.task_table; a render that counts them on the way, p.tile_cost
+// skip (may be null): [local tile] 1 = provably empty, left out of the task list and
+// of cost 0; cull_id: the flags' id (CullState::serial; 0: none)
 template <typename R>
 int lpt_prepare(rtw_ctx* c, rtw::KParams<R>& p, const rtw::RenderPlan& pl, const LptKey& key, bool split_has_costs,
-                hipStream_t stream);
+                hipStream_t stream, const uint8_t* skip = nullptr, uint32_t cull_id = 0);
 // capi_lpt.cpp: after the launch of a render that counts (p.tile_cost)
 int lpt_counted(rtw_ctx* c, const LptKey& key, hipStream_t stream);
 // capi_lpt.cpp: the tile costs the context counted for (cam, rank, nranks) under

@@ -77,7 +77,7 @@ int lpt_pilot(rtw_ctx* c, const rtw::KParams<R>& p, const rtw::RenderPlan& pl, h
 
 template <typename R>
 int lpt_prepare(rtw_ctx* c, rtw::KParams<R>& p, const rtw::RenderPlan& pl, const LptKey& key, bool split_has_costs,
-                hipStream_t stream) {
+                hipStream_t stream, const uint8_t* skip, uint32_t cull_id) {
     const rtw::RenderKnobs& k = c->knobs;
     LptCache& l = c->lpt;
     const uint32_t nt = p.n_local_tiles;
@@ -94,7 +94,8 @@ int lpt_prepare(rtw_ctx* c, rtw::KParams<R>& p, const rtw::RenderPlan& pl, const
     case rtw::kSplitCosts:
         // a split dealt by tile costs: those costs order this rank's tasks
         l.st.h_cost.resize(nt);
-        for (uint32_t t = 0; t < nt; ++t) l.st.h_cost[t] = c->split.cost[c->split.h_tile_map[t]];
+        for (uint32_t t = 0; t < nt; ++t)
+            l.st.h_cost[t] = skip && skip[t] ? 0u : c->split.cost[c->split.h_tile_map[t]];
         l.st.adopt(key);
         break;
     case rtw::kCountInline:
@@ -116,6 +117,9 @@ int lpt_prepare(rtw_ctx* c, rtw::KParams<R>& p, const rtw::RenderPlan& pl, const
         rc = lpt_pilot(c, p, pl, stream);
         lap("pilot", nt, "tiles");
         if (rc) return rc;
+        // (the pilot traces every tile; a provably empty one costs nothing in the render)
+        for (uint32_t t = 0; skip && t < nt; ++t)
+            if (skip[t]) l.st.h_cost[t] = 0;
         l.st.adopt(key);
         HIP_TRY(c, hipMemsetAsync(c->d_counters, 0, rtw::kCounters * sizeof(unsigned long long), stream));
         break;
@@ -129,23 +133,25 @@ int lpt_prepare(rtw_ctx* c, rtw::KParams<R>& p, const rtw::RenderPlan& pl, const
     }
     if (!l.st.valid) return RTW_OK;   // (this render counts: the plain tile order)
     const uint64_t target = k.target_tasks ? k.target_tasks : rtw::kAutoTasks;
-    if (l.st.table_stale(p.n_chunks, k.group, target)) {
+    if (l.st.table_stale(p.n_chunks, k.group, target, cull_id)) {
         l.st.tab_valid = false;
-        l.st.h_tasks = rtw::build_task_list(l.st.h_cost, p.n_chunks, k.group ? p.group : 0u, target, k);
-        rc = ensure(c, &l.d_tasks, &l.tasks_cap, l.st.h_tasks.size() * sizeof(uint32_t));
+        l.st.h_tasks = rtw::build_task_list(l.st.h_cost, p.n_chunks, k.group ? p.group : 0u, target, k, skip);
+        rc = ensure(c, &l.d_tasks, &l.tasks_cap, std::max<size_t>(l.st.h_tasks.size(), 2) * sizeof(uint32_t));
         if (rc) return rc;
         HIP_TRY(c, hipMemcpyAsync(l.d_tasks, l.st.h_tasks.data(), l.st.h_tasks.size() * sizeof(uint32_t),
                                   hipMemcpyHostToDevice, stream));
         HIP_TRY(c, hipStreamSynchronize(stream));
         lap("tasks", l.st.h_tasks.size() / 2, "tasks");
-        l.st.table_built(p.n_chunks, k.group, target);
+        l.st.table_built(p.n_chunks, k.group, target, cull_id);
     }
     p.task_table = reinterpret_cast<const uint32_t*>(l.d_tasks);
     p.n_tasks = (uint32_t)(l.st.h_tasks.size() / 2);
     return RTW_OK;
 }
-template int lpt_prepare<float>(rtw_ctx*, rtw::KParams<float>&, const rtw::RenderPlan&, const LptKey&, bool, hipStream_t);
-template int lpt_prepare<double>(rtw_ctx*, rtw::KParams<double>&, const rtw::RenderPlan&, const LptKey&, bool, hipStream_t);
+template int lpt_prepare<float>(rtw_ctx*, rtw::KParams<float>&, const rtw::RenderPlan&, const LptKey&, bool, hipStream_t,
+                                const uint8_t*, uint32_t);
+template int lpt_prepare<double>(rtw_ctx*, rtw::KParams<double>&, const rtw::RenderPlan&, const LptKey&, bool, hipStream_t,
+                                 const uint8_t*, uint32_t);
 
 // the counts are complete after lpt.ev, read back by the next render of the same key
 int lpt_counted(rtw_ctx* c, const LptKey& key, hipStream_t stream) {
@@ -169,7 +175,13 @@ int tile_costs_of(rtw_ctx* c, const rtw_camera* cam, uint32_t rank, uint32_t nra
         if (rc) return rc;
     }
     if (st.h_cost.size() != tiles.size()) return fail(c, RTW_E_INVALID, "tile cost count mismatch");
-    for (size_t k = 0; k < tiles.size(); ++k) cost[tiles[k]] = st.h_cost[k];
+    // A provably empty tile was never traced and counted nothing: it is reported with the
+    // smallest cost, 1 -- the fold answers it -- so that 0 keeps meaning "not counted"
+    const LptKey key = lpt_key(c, cam, rank, nranks);
+    const rtw::CullState& cs = c->cull.st;
+    const bool culled = cs.has(key) && cs.flags.size() == tiles.size();
+    for (size_t k = 0; k < tiles.size(); ++k)
+        cost[tiles[k]] = culled && cs.flags[k] && !st.h_cost[k] ? 1u : st.h_cost[k];
     return RTW_OK;
 }
 

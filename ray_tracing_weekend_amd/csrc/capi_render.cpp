@@ -32,6 +32,52 @@ int ensure_tile_map(rtw_ctx* c, uint32_t W, uint32_t H, uint32_t rank, uint32_t 
     return RTW_OK;
 }
 
+// The flags of the provably empty tiles of `key` (host/tile_cull.hpp), on the
+// host and the device: classified once per key, dropped with it.  The device
+// copies are rewritten only after the device is idle (upload_map's reason).
+int cull_prepare(rtw_ctx* c, const LptKey& key, uint32_t rank, uint32_t nranks) {
+    CullCache& k = c->cull;
+    if (k.st.has(key)) return RTW_OK;
+    std::vector<uint32_t> tiles;
+    c->split.local_tiles(key.cam.image_width, key.cam.image_height, rank, nranks, tiles);
+    rtw::cull_classify(k.st, key, *c->cull_scene, tiles);
+    if (!k.st.n_culled) return RTW_OK;
+    auto upload = [&]() -> int {
+        HIP_TRY(c, hipDeviceSynchronize());
+        const int rc = ensure(c, &k.d_flags, &k.flags_cap, align_up(k.st.flags.size(), 64));
+        if (rc) return rc;
+        HIP_TRY(c, hipMemcpy(k.d_flags, k.st.flags.data(), k.st.flags.size(), hipMemcpyHostToDevice));
+        return RTW_OK;
+    };
+    const int rc = upload();
+    if (rc) k.st.drop();
+    return rc;
+}
+
+// A render of a key with provably empty tiles and no longest-first task list
+// (its first render, or a render too short for one): the plain tile order
+// without those tiles, as a task table.
+template <typename R>
+int cull_plain_tasks(rtw_ctx* c, rtw::KParams<R>& p) {
+    CullCache& k = c->cull;
+    if (!k.st.tab_valid || k.st.tab_chunks != p.n_chunks || k.st.tab_group != p.group) {
+        k.st.tab_valid = false;
+        k.st.h_tasks = rtw::plain_task_list(k.st.flags, p.n_chunks, p.group);
+        HIP_TRY(c, hipDeviceSynchronize());
+        const int rc = ensure(c, &k.d_tasks, &k.tasks_cap, std::max<size_t>(k.st.h_tasks.size(), 2) * sizeof(uint32_t));
+        if (rc) return rc;
+        if (!k.st.h_tasks.empty())
+            HIP_TRY(c, hipMemcpy(k.d_tasks, k.st.h_tasks.data(), k.st.h_tasks.size() * sizeof(uint32_t),
+                                 hipMemcpyHostToDevice));
+        k.st.tab_chunks = p.n_chunks;
+        k.st.tab_group = p.group;
+        k.st.tab_valid = true;
+    }
+    p.task_table = reinterpret_cast<const uint32_t*>(k.d_tasks);
+    p.n_tasks = (uint32_t)(k.st.h_tasks.size() / 2);
+    return RTW_OK;
+}
+
 // The chunk-sum buffer of a render, and the plan for the chunk it holds: when
 // the device cannot hold it (other allocations) an auto chunk doubles instead
 // of failing -- stats.chunk reports it, the fold is then chunk-associated
@@ -87,18 +133,31 @@ int render_pass_t(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t ran
     // (a later pass of the same render: the counters go on, but the task counter starts over)
     HIP_TRY(c, pass.begin ? hipMemsetAsync(c->d_counters, 0, rtw::kCounters * sizeof(unsigned long long), stream)
                           : hipMemsetAsync(c->d_counters + rtw::kCounterNextTask, 0, sizeof(unsigned long long), stream));
-    // task order
     const rtw_camera key_cam = rtw::key_camera(*cam, pass);
     const LptKey key = lpt_key(c, &key_cam, rank, nranks);
+    const bool dark = p.spp == 0 || p.max_depth == 0;   // every sample is Colour::default() + res = 0 (camera.rs:470-472)
+    // provably empty tiles (f64 sphere + plane kernels): no task, the fold answers them
+    const rtw::CullState* cull = nullptr;
+    if (kind.cull && sizeof(R) == 8 && c->knobs.tile_cull && c->cull_scene && nt && !dark && !pl.err &&
+        !(pl.opts & (rtw::dev::kOptPrims | rtw::dev::kOptTex)) && p.n_chunks < (1u << 20)) {
+        rc = cull_prepare(c, key, rank, nranks);
+        if (rc) return rc;
+        if (c->cull.st.n_culled) cull = &c->cull.st;
+    }
+    // task order
     if (pl.lpt && kind.lpt) {
-        rc = lpt_prepare(c, p, pl, key, split && !c->split.cost.empty(), stream);
+        rc = lpt_prepare(c, p, pl, key, split && !c->split.cost.empty(), stream, cull ? cull->flags.data() : nullptr,
+                         cull ? cull->serial : 0u);
+        if (rc) return rc;
+    }
+    if (cull && !p.task_table) {
+        rc = cull_plain_tasks(c, p);
         if (rc) return rc;
     }
     // launch
     hipEvent_t* ev = c->ring[c->n_renders % rtw_ctx::kRing];
     if (pass.begin) HIP_TRY(c, hipEventRecord(c->ev0, stream));
     HIP_TRY(c, hipEventRecord(ev[0], stream));
-    const bool dark = p.spp == 0 || p.max_depth == 0;   // every sample is Colour::default() + res = 0 (camera.rs:470-472)
     int lrc = 0;
     if (nt == 0 || (dark && kind.zero_fill)) {
         if (nt) HIP_TRY(c, hipMemsetAsync(d_out, 0, rtw::packed_bytes(nt, sizeof(R)), stream));
@@ -106,8 +165,9 @@ int render_pass_t(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t ran
     } else {
         if (dark) p.n_tasks = p.n_chunks = 0;
         lrc = rtw::launch_render(p, pl.world, pl.opts, pl.launch_lds,
-                                 rtw::Fold<R>{kind.fold, reinterpret_cast<R*>(d_out), pass.accum, pass.first}, stream,
-                                 ev[1]);
+                                 rtw::Fold<R>{kind.fold, reinterpret_cast<R*>(d_out), pass.accum, pass.first,
+                                              cull ? reinterpret_cast<const uint8_t*>(c->cull.d_flags) : nullptr},
+                                 stream, ev[1]);
     }
     if (lrc < 0) return fail(c, RTW_E_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
     // (the launcher reports the instantiation it launched, not what it was asked for)
@@ -128,6 +188,10 @@ int render_pass_t(rtw_ctx* c, const rtw_camera* cam, uint64_t seed, uint32_t ran
     const uint64_t before = pass.begin ? 0 : c->last.samples;
     c->last = rtw_stats{};
     c->last.samples = before + rtw::tile_pixels(W, H, tiles) * p.spp;
+    // (a culled sample is one segment that misses everything: credited here, the kernel never saw it)
+    c->last_culled = cull ? cull->n_culled : 0u;
+    if (pass.begin) c->cull_segments = 0;
+    if (cull) c->cull_segments += cull->culled_pixels * p.spp;
     c->last.accel = (uint32_t)pl.accel;
     c->last.bvh_width = pl.bvh_width;
     c->last.kernel = (uint32_t)pl.world;

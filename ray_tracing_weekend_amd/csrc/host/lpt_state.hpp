@@ -35,6 +35,7 @@ struct LptState {
     bool tab_valid = false;           // h_tasks is the task list of (h_cost, tab_*)
     uint32_t tab_chunks = 0, tab_group = 0;
     uint64_t tab_target = 0;
+    uint32_t tab_cull = 0;            // the tile flags it leaves out (CullState::serial; 0: none)
     std::vector<uint32_t> h_tasks;
 
     // the context holds (or has pending) tile costs of this key
@@ -59,15 +60,16 @@ struct LptState {
         if (ok) valid = true;
     }
 
-    // the task list is not the one of (h_cost, n_chunks, group, target)
-    bool table_stale(uint32_t n_chunks, uint32_t group, uint64_t target) const {
-        return !tab_valid || tab_chunks != n_chunks || tab_group != group || tab_target != target;
+    // the task list is not the one of (h_cost, n_chunks, group, target, the culled tiles left out)
+    bool table_stale(uint32_t n_chunks, uint32_t group, uint64_t target, uint32_t cull = 0) const {
+        return !tab_valid || tab_chunks != n_chunks || tab_group != group || tab_target != target || tab_cull != cull;
     }
-    void table_built(uint32_t n_chunks, uint32_t group, uint64_t target) {
+    void table_built(uint32_t n_chunks, uint32_t group, uint64_t target, uint32_t cull = 0) {
         tab_valid = true;
         tab_chunks = n_chunks;
         tab_group = group;
         tab_target = target;
+        tab_cull = cull;
     }
 };
 

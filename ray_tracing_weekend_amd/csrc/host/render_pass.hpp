@@ -25,11 +25,13 @@ struct PassKindRow {
     bool zero_fill;     // no sample to trace (no samples, or depth 0: every sample is 0):
                         // d_out is zeroed and nothing is launched (false: the launch
                         // without tasks -- its fold alone)
+    bool cull;          // provably empty tiles get no task (host/tile_cull.hpp): the pass's
+                        // own fold answers them (adaptive: the caller folds, so never)
 };
 constexpr PassKindRow kPassKinds[] = {
-    /* kPassOneShot  */ {false, true, true, kFoldReduce, true},
-    /* kPassWindow   */ {true, true, true, kFoldWindow, false},
-    /* kPassAdaptive */ {true, false, false, kFoldNone, false},
+    /* kPassOneShot  */ {false, true, true, kFoldReduce, true, true},
+    /* kPassWindow   */ {true, true, true, kFoldWindow, false, true},
+    /* kPassAdaptive */ {true, false, false, kFoldNone, false, false},
 };
 
 // The samples [first, first + n) of every pixel of the pass's tiles.

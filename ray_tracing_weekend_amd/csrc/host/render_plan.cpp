@@ -267,13 +267,15 @@ template RenderPlan plan_render<double>(const RenderKnobs&, const DevScene<doubl
 // chunk) folded in sample order by the reduce, the image is the same bit for
 // bit.  Entry: {local tile, first chunk | chunks << 20}.
 std::vector<uint32_t> build_task_list(const std::vector<uint32_t>& cost, uint32_t n_chunks, uint32_t fixed_group,
-                                      uint64_t target, const RenderKnobs& c) {
+                                      uint64_t target, const RenderKnobs& c, const uint8_t* skip) {
     const uint32_t nt = (uint32_t)cost.size();
-    std::vector<uint32_t> order(nt);
-    for (uint32_t k = 0; k < nt; ++k) order[k] = k;
+    std::vector<uint32_t> order;
+    order.reserve(nt);
+    for (uint32_t k = 0; k < nt; ++k)
+        if (!skip || !skip[k]) order.push_back(k);
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return cost[a] > cost[b]; });
     double total = 0;
-    for (uint32_t k = 0; k < nt; ++k) total += std::max<uint32_t>(cost[k], 1);
+    for (uint32_t k : order) total += std::max<uint32_t>(cost[k], 1);
     const double per_task = total * n_chunks / (double)std::max<uint64_t>(target, 1);   // pilot-cost units x chunks
     std::vector<uint32_t> tab;
     if (!fixed_group && c.guide_div) {

@@ -89,6 +89,9 @@ struct RenderKnobs {
     uint32_t cost_time = 1;           // tile costs in wave-time shares (KParams::cost_time); 0: work counts
     uint64_t guide_floor = 1u << 20;
     uint32_t balance = 1;             // multi-device renders: deal tiles by their counted costs
+    uint32_t tile_cull = 1;           // f64 sphere + plane renders: tiles whose camera beam provably
+                                      // misses the scene get no task, the fold answers them
+                                      // (host/tile_cull.hpp); 0: off
     static constexpr int64_t kWindowAuto = -1;
     int64_t window = 0;               // sample windows (plan_windows): 0 off; N > 0: renders of more
                                       // than N samples per pixel run N at a time onto an f64
@@ -151,7 +154,10 @@ RenderPlan plan_render(const RenderKnobs& k, const DevScene<R>& sc, const rtw_ca
 
 // The longest-tiles-first task list of tiles with these costs:
 // {local tile, first chunk | chunks << 20} pairs.  fixed_group 0: sized by cost.
+// skip (may be null): [local tile] 1 = the tile gets no task (provably empty,
+// host/tile_cull.hpp) and weighs nothing, whatever its cost; a cost of 0 alone
+// is a cheap tile like any other.
 std::vector<uint32_t> build_task_list(const std::vector<uint32_t>& cost, uint32_t n_chunks, uint32_t fixed_group,
-                                      uint64_t target, const RenderKnobs& k);
+                                      uint64_t target, const RenderKnobs& k, const uint8_t* skip = nullptr);
 
 }  // namespace rtw

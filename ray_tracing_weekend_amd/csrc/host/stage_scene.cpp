@@ -181,7 +181,8 @@ void box_derive(const double* b, double* out) {
 // host staging blob, and fill the DevScene pointers relative to `base`.
 template <typename R>
 std::vector<unsigned char> stage_scene(const rtw_scene* s, rtw::DevScene<R>* ds, uintptr_t base,
-                                       uint32_t leaf_max, uint32_t light_leaf, double grid_density) {
+                                       uint32_t leaf_max, uint32_t light_leaf, double grid_density,
+                                       rtw::BvhBuild* keep_bvh) {
     using R4 = rtw::R4<R>;
     size_t off = 0;
     auto reserve = [&](size_t bytes) {
@@ -527,13 +528,14 @@ std::vector<unsigned char> stage_scene(const rtw_scene* s, rtw::DevScene<R>* ds,
     ds->n_lights = s->n_lights;
     ds->n_nodes = (uint32_t)bb.nodes.size();
     ds->bvh_depth = bb.depth;
+    if (keep_bvh) *keep_bvh = bb;
     return blob;
 }
 
 template std::vector<unsigned char> stage_scene<float>(const rtw_scene*, DevScene<float>*, uintptr_t, uint32_t,
-                                                       uint32_t, double);
+                                                       uint32_t, double, BvhBuild*);
 template std::vector<unsigned char> stage_scene<double>(const rtw_scene*, DevScene<double>*, uintptr_t, uint32_t,
-                                                        uint32_t, double);
+                                                        uint32_t, double, BvhBuild*);
 
 int validate_scene(const rtw_scene* s, std::string* msg) {
     auto fail = [msg](int code, const char* text) {

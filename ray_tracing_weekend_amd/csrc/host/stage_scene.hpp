@@ -11,6 +11,7 @@
 
 #include "../../../include/rtw.h"
 #include "../rtw_kernels.h"
+#include "bvh.hpp"
 
 namespace rtw {
 
@@ -21,13 +22,15 @@ void box_derive(const double* b, double* out);
 
 // Convert the caller's f64 SoA into the device layout of precision R, in one
 // host staging blob, and fill the DevScene pointers relative to `base`.
+// keep_bvh (may be null) receives the binary BVH over the spheres that was
+// staged (the tile classifier walks it on the host, host/tile_cull.hpp).
 template <typename R>
 std::vector<unsigned char> stage_scene(const rtw_scene* s, DevScene<R>* ds, uintptr_t base, uint32_t leaf_max,
-                                       uint32_t light_leaf, double grid_density);
+                                       uint32_t light_leaf, double grid_density, BvhBuild* keep_bvh = nullptr);
 extern template std::vector<unsigned char> stage_scene<float>(const rtw_scene*, DevScene<float>*, uintptr_t,
-                                                              uint32_t, uint32_t, double);
+                                                              uint32_t, uint32_t, double, BvhBuild*);
 extern template std::vector<unsigned char> stage_scene<double>(const rtw_scene*, DevScene<double>*, uintptr_t,
-                                                               uint32_t, uint32_t, double);
+                                                               uint32_t, uint32_t, double, BvhBuild*);
 
 // RTW_OK, or the error code with its text in *msg
 int validate_scene(const rtw_scene* s, std::string* msg);

@@ -1568,7 +1568,8 @@ template <typename R>
 constexpr uint32_t kFoldWindow = sizeof(R) == 4 ? 16 : RTW_FOLD_WIN64;
 
 template <typename R>
-__global__ void __launch_bounds__(64) reduce_chunks_kernel(const KParams<R> p, R* __restrict__ out) {
+__global__ void __launch_bounds__(64) reduce_chunks_kernel(const KParams<R> p, R* __restrict__ out,
+                                                           const uint8_t* __restrict__ cull) {
     constexpr uint32_t kFoldWin = kFoldWindow<R>;
     constexpr uint32_t kFoldRow = kFoldWin * 3 + 1;    // LDS row (odd: no bank conflicts)
     // one wave per tile; a pixel's chunk sums are contiguous (the sample-major
@@ -1584,8 +1585,15 @@ __global__ void __launch_bounds__(64) reduce_chunks_kernel(const KParams<R> p, R
     const size_t row_len = (size_t)p.n_chunks * 3;
     const R* tile = p.partial + (size_t)lt * 64 * row_len;
     double sx = 0, sy = 0, sz = 0;
+    // a provably empty tile (block-uniform): its chunk sums were never written
+    const bool empty = cull && cull[lt];
+    if (empty) {
+        sx = fold_constant<R>(sx, miss_colour(p.bg[0]), p.spp, p.chunk);
+        sy = fold_constant<R>(sy, miss_colour(p.bg[1]), p.spp, p.chunk);
+        sz = fold_constant<R>(sz, miss_colour(p.bg[2]), p.spp, p.chunk);
+    }
     constexpr uint32_t kNv = kFoldWin * 3;
-    for (uint32_t c0 = 0; c0 < p.n_chunks; c0 += kFoldWin) {
+    for (uint32_t c0 = 0; c0 < (empty ? 0u : p.n_chunks); c0 += kFoldWin) {
         const uint32_t kw = min(kFoldWin, p.n_chunks - c0), nv = kw * 3;
         const R* src = tile + (size_t)c0 * 3;
         if (kw == kFoldWin) {
@@ -1633,7 +1641,8 @@ __global__ void __launch_bounds__(64) reduce_chunks_kernel(const KParams<R> p, R
 // after another are the one-shot fold at the same chunk, addition by addition.
 template <typename R>
 __global__ void __launch_bounds__(64) fold_window_kernel(const KParams<R> p, double* __restrict__ accum,
-                                                         uint32_t first_sample, R* __restrict__ out) {
+                                                         uint32_t first_sample, R* __restrict__ out,
+                                                         const uint8_t* __restrict__ cull) {
     constexpr uint32_t kFoldWin = kFoldWindow<R>;
     constexpr uint32_t kFoldRow = kFoldWin * 3 + 1;    // LDS row (odd: no bank conflicts)
     __shared__ R win[64 * kFoldRow];
@@ -1650,8 +1659,15 @@ __global__ void __launch_bounds__(64) fold_window_kernel(const KParams<R> p, dou
         sy = acc[1];
         sz = acc[2];
     }
+    // a provably empty tile (block-uniform), as reduce_chunks_kernel: the window's samples onto the carry
+    const bool empty = cull && cull[lt];
+    if (empty) {
+        sx = fold_constant<R>(sx, miss_colour(p.bg[0]), p.spp, p.chunk);
+        sy = fold_constant<R>(sy, miss_colour(p.bg[1]), p.spp, p.chunk);
+        sz = fold_constant<R>(sz, miss_colour(p.bg[2]), p.spp, p.chunk);
+    }
     constexpr uint32_t kNv = kFoldWin * 3;
-    for (uint32_t c0 = 0; c0 < p.n_chunks; c0 += kFoldWin) {
+    for (uint32_t c0 = 0; c0 < (empty ? 0u : p.n_chunks); c0 += kFoldWin) {
         const uint32_t kw = min(kFoldWin, p.n_chunks - c0), nv = kw * 3;
         const R* src = tile + (size_t)c0 * 3;
         if (kw == kFoldWin) {

@@ -95,10 +95,10 @@ inline int launch_render_impl(const KParams<R>& p_in, int world, int opts, size_
     if (fold.kind == kFoldNone || !p_in.n_local_tiles) return ran;
     if (fold.kind == kFoldWindow)
         hipLaunchKernelGGL((dev::fold_window_kernel<R>), dim3(p_in.n_local_tiles), dim3(64), 0, stream, p_in,
-                           fold.accum, fold.first_sample, fold.out);
+                           fold.accum, fold.first_sample, fold.out, fold.cull);
     else
         hipLaunchKernelGGL((dev::reduce_chunks_kernel<R>), dim3(p_in.n_local_tiles), dim3(64), 0, stream, p_in,
-                           fold.out);
+                           fold.out, fold.cull);
     return hipGetLastError() != hipSuccess ? -1 : ran;
 }
 

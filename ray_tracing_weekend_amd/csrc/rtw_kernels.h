@@ -393,7 +393,31 @@ struct Fold {
     R* out;                           // (window: may be null)
     double* accum;
     uint32_t first_sample;            // window: where it starts in the render
+    // non-null: [local tile] 1 = provably empty (host/tile_cull.hpp): the render kernel got
+    // no task for it, and the fold takes fold_constant instead of reading its chunk sums
+    const uint8_t* cull = nullptr;
 };
+// The fold of a provably empty tile's pixel: every sample is the render kernel's
+// miss expression with mult = (1, 1, 1), res = +0 -- col = 1 * bg + 0 in R -- so
+// the pixel is `sum` (the samples before: 0, a window's carry) + the chunk sums
+// of n samples of col at `chunk` samples per item: each chunk sum 0 + col, + col
+// per further sample in R (a short last chunk included), the running sum taking
+// them in chunk order in f64.  The render kernel's and the fold kernels'
+// additions, one by one, at any chunk, window and spp.
+template <typename R>
+__host__ __device__ inline double fold_constant(double sum, R col, uint32_t n, uint32_t chunk) {
+    for (uint32_t s = 0; s < n; s += chunk) {
+        const uint32_t m = n - s < chunk ? n - s : chunk;
+        R cs = R(0) + col;
+        for (uint32_t k = 1; k < m; ++k) cs = cs + col;
+        sum = sum + (double)cs;
+    }
+    return sum;
+}
+template <typename R>
+__host__ __device__ inline R miss_colour(R bg) {
+    return R(1) * bg + R(0);
+}
 // Host-side launch helpers (defined in render_f32.hip / render_f64.hip): the
 // render kernel <world, opts> of the plan (RenderPlan::world, opts) with
 // lds_bytes of dynamic LDS (p.n_tasks 0: no kernel), `mid` (may be null)
