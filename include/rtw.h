@@ -673,6 +673,91 @@ int rtw_render_features_device(rtw_ctx *ctx, const rtw_camera *cam, uint64_t see
                                double *d_features, size_t features_bytes, int32_t *d_ids, size_t ids_bytes,
                                void *stream);
 
+/* ---- denoising: an edge-avoiding a-trous filter over the feature buffers ----
+ * Reads a render's colour sums, the feature sums of rtw_render_features for the
+ * same samples and the sample counts, and writes the filtered per-sample MEAN
+ * [H, W, 3] f64 (encode it with spp = 1).  No scene is needed.  The filter is
+ * f64 arithmetic in both precisions; every operation below is one separately
+ * rounded f64 operation, never contracted, in the written order, and
+ * "x > y ? x : y" is that comparison and select, never fmax.  Image order, j = 0
+ * the bottom row.
+ *
+ * Per pixel p: colour sums S[3] (f32 sums are widened exactly), feature sums
+ * F[8], the count n = counts[p], or spp when counts is NULL; nd = (double)n.
+ * Prepare:
+ *   guide_ok = n > 0 and all 8 of F finite.  A pixel that is not guide_ok is
+ *              never a tap source; its output is S / nd, or (0, 0, 0) when n == 0.
+ *   c = S / nd;  valid = guide_ok and all of c finite
+ *   alb_k = F[k] / nd;  a_k = alb_k > 2^-10 ? alb_k : 2^-10;  demodulate == 0: a_k = 1
+ *   e_k = c_k / a_k            (the irradiance; of no account when not valid)
+ *   len = sqrt((F3*F3 + F4*F4) + F5*F5);  N = len > 0 ? F[3..5] / len : 0
+ *   d = F7 > 0 ? F6 / F7 : 0
+ * Iteration k = 0 .. iterations - 1, step = 2^k, s_k = sigma_colour * 2^-k,
+ * sc2_k = s_k * s_k (on the host), h = {1/16, 1/4, 3/8, 1/4, 1/16}.  A centre p
+ * that is guide_ok visits the taps q = p + (dx, dy) * step, dy = -2..2 outer,
+ * dx = -2..2 inner, and skips a tap outside the image, one whose pixel is not
+ * guide_ok and one whose pixel is not valid now (a skipped tap adds nothing;
+ * it is never multiplied by 0).  Else:
+ *   w_n: both normals all zero: 1.  Otherwise t = (Np.x*Nq.x + Np.y*Nq.y) +
+ *        Np.z*Nq.z;  t = t > 0 ? t : 0;  t = t * t, normal_power_log2 times;  w_n = t
+ *   w_d: mx = dp > dq ? dp : dq.  mx > 0: r = fabs(dp - dq) / mx;  x = r /
+ *        sigma_depth;  u = 1 - x*x;  u = u > 0 ? u : 0;  w_d = u * u.  Otherwise 1
+ *   w_c: 1 when sigma_colour == 0 or the centre is not valid.  Otherwise g_k =
+ *        ep_k - eq_k;  s = (g0*g0 + g1*g1) + g2*g2;  w_c = 1 / (1 + s / sc2_k)
+ *   w = (((h[dy+2] * h[dx+2]) * w_n) * w_d) * w_c
+ *   num_k = num_k + w * eq_k;  den = den + w
+ * After the taps a valid centre takes e'_k = num_k / den (its own tap is a
+ * source).  A guide_ok centre that is not valid becomes valid with e' = num /
+ * den when fill_nonfinite and den > 0, and is a source from the next iteration
+ * on; otherwise it stays as it is.  Iteration k reads the colours of iteration
+ * k - 1 and writes another array; the guides do not change.
+ * Finish: a valid pixel outputs e_k * a_k; a guide_ok pixel that never became
+ * valid outputs S / nd, so the caller sees its NaN.
+ *
+ * counts may be NULL (spp > 0 then); params may be NULL (the defaults of
+ * rtw_denoise_params_default).  sums_precision: RTW_F32 (what an f32 context's
+ * rtw_render_image_device writes) or RTW_F64 (the adaptive, window and host
+ * entries).  On a multi-device or virtual-rank context the filter runs on the
+ * first device, where the gathered image is.  The filter keeps its own buffers:
+ * a render, a query or a feature pass before and after it is unchanged.
+ * Tuning key denoise_lds: 0 every iteration reads its taps from global memory,
+ * 2 every iteration whose tile and halo fit stages them in LDS, 1 (default)
+ * the plan's choice; the result is the same bit for bit.
+ *
+ * Errors: RTW_E_INVALID -- before any device call -- for a NULL context, sums,
+ * features or out; iterations outside 1..16, normal_power_log2 above 10,
+ * sigma_colour negative, sigma_depth not positive, either infinite or NaN,
+ * demodulate or fill_nonfinite above 1; counts NULL with spp 0; a width or
+ * height of 2^16 or more; (device form) a buffer that is too small, a pointer
+ * that is not 16-byte aligned, d_out overlapping an input.  The host form is
+ * synchronous; the device form enqueues on `stream` as rtw_render_device does
+ * and never waits for the device. */
+typedef struct rtw_denoise_params {
+    uint32_t iterations;          /* 1..16 */
+    uint32_t normal_power_log2;   /* 0..10: the normal weight is the clamped cosine to the power 2^this */
+    double sigma_colour;          /* >= 0; 0: no colour weight */
+    double sigma_depth;           /* > 0: relative distance difference at which the depth weight is 0 */
+    uint32_t demodulate;          /* 1: filter colour / first-hit albedo */
+    uint32_t fill_nonfinite;      /* 1: non-finite pixels take their neighbours' filtered colour */
+} rtw_denoise_params;
+/* iterations 5, normal_power_log2 5, sigma_colour 0.5, sigma_depth 0.125, demodulate 1, fill_nonfinite 1 */
+void rtw_denoise_params_default(rtw_denoise_params *out);
+int rtw_denoise(rtw_ctx *ctx, const double *sums, const double *features, const uint32_t *counts, uint32_t spp,
+                uint32_t width, uint32_t height, const rtw_denoise_params *params, double *out);
+int rtw_denoise_device(rtw_ctx *ctx, const void *d_sums, int sums_precision, size_t sums_bytes,
+                       const double *d_features, size_t features_bytes, const uint32_t *d_counts, size_t counts_bytes,
+                       uint32_t spp, uint32_t width, uint32_t height, const rtw_denoise_params *params,
+                       double *d_out, size_t out_bytes, void *stream);
+typedef struct rtw_denoise_stats {
+    uint32_t iterations;          /* of the last denoise */
+    uint32_t lds_iterations;      /* ... that staged their taps in LDS */
+    uint64_t filled;              /* guide_ok pixels that were not valid and became valid */
+    uint64_t left_nonfinite;      /* pixels whose output has a non-finite channel */
+    double kernel_ms;             /* device time of the whole pass (HIP events) */
+} rtw_denoise_stats;
+/* Counters of the last denoise (waits for it); RTW_E_INVALID before the first. */
+int rtw_get_denoise_stats(rtw_ctx *ctx, rtw_denoise_stats *stats);
+
 /* ---- scenes::simple (scenes/src/lib.rs:155-233) ----------------------- */
 /* The library owns the arrays; view them through rtw_world_scene(). grid_n =
  * 11 is the reference scene; larger n gives the synthetic C3/C5 fields. */

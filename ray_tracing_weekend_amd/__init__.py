@@ -32,7 +32,7 @@ __all__ = [
     "Quad", "Cuboid", "Transformation", "translation", "rotation", "SolidColour", "CheckerTexture",
     "NoiseTexture", "Perlin", "HittableList", "BoundedVolumeHierarchy", "SceneSoA", "flatten",
     "CameraBuilder", "Camera", "Renderer", "scenes", "encode_rgb8", "write_ppm", "RenderError",
-    "RTW_F32", "RTW_F64", "feature_means",
+    "RTW_F32", "RTW_F64", "feature_means", "DenoiseParams",
 ]
 
 _lib = _capi.load()   # raises if librtw.so is missing: there is no CPU fallback
@@ -549,6 +549,19 @@ class Camera:
             r.set_scene(flatten(world, lights))
             return r.render_features(self, seed, first, n, counts=counts, want_ids=want_ids)
 
+    def render_denoised(self, world, lights, *, seed: int = 0x5EED0001, precision: int = RTW_F64, device: int = 0,
+                        accel: int = RTW_ACCEL_AUTO, **params) -> np.ndarray:
+        """The render, its feature pass and the denoiser on one context: the
+        filtered per-sample means [H, W, 3] float64 of Renderer.render's sums
+        and Renderer.render_features' guides of the same samples (display them
+        with spp = 1).  **params as Renderer.denoise's."""
+        with Renderer(device=device, precision=precision) as r:
+            r.set_accel(accel)
+            r.set_scene(flatten(world, lights))
+            sums = r.render(self, seed)
+            features, _ = r.render_features(self, seed, want_ids=False)
+            return r.denoise(sums, features, int(self.raw.samples_per_pixel), **params)
+
 
 class Renderer:
     """An rtw_ctx: a device (or, with `devices`, one rank per listed GPU:
@@ -949,6 +962,66 @@ class Renderer:
             ids.ctypes.data_as(C.c_void_p) if ids is not None else None), "rtw_render_features")
         return features, ids
 
+    # ---- the denoiser (rtw_denoise)
+    def denoise(self, sums, features, n, **params):
+        """The edge-avoiding a-trous filter of include/rtw.h over a render's
+        colour sums [H, W, 3], the feature sums [H, W, 8] of render_features
+        for the same samples and n, the sample count or the [H, W] counts of an
+        adaptive render: the filtered per-sample MEANS [H, W, 3] float64
+        (display them with spp = 1).  Keyword parameters as DenoiseParams
+        (iterations, normal_power_log2, sigma_colour, sigma_depth, demodulate,
+        fill_nonfinite); those left out take the library's defaults.  numpy
+        arrays go through the host entry (float32 sums are widened exactly
+        first); torch GPU tensors -- float32 or float64 sums, float64 features,
+        int32 / uint32 counts -- go through the device entry on torch's current
+        stream, without a host copy, and a torch tensor comes back.  No scene
+        is needed; on a multi-device Renderer the filter runs on the first
+        device."""
+        p = DenoiseParams(**params).raw
+        if type(sums).__module__.split(".")[0] == "torch":
+            import torch
+            H, W = int(sums.shape[0]), int(sums.shape[1])
+            per_pixel = type(n).__module__.split(".")[0] == "torch"
+            checks = [(sums, (torch.float32, torch.float64), (H, W, 3), "sums"),
+                      (features, (torch.float64,), (H, W, 8), "features")]
+            if per_pixel:
+                checks.append((n, (torch.int32, getattr(torch, "uint32", torch.int32)), (H, W), "counts"))
+            for a, dts, shape, what in checks:
+                if not (type(a).__module__.split(".")[0] == "torch" and a.dtype in dts and a.is_cuda
+                        and a.device.index == self.device and a.is_contiguous() and tuple(a.shape) == shape):
+                    raise RenderError(_capi.RTW_E_INVALID, f"denoise: {what} must be a contiguous {list(shape)} "
+                                      f"tensor of {dts} on device {self.device}")
+            out = torch.empty((H, W, 3), dtype=torch.float64, device=sums.device)
+            stream = _torch_stream(self.device)
+            self._check(_lib.rtw_denoise_device(
+                self.ctx, C.c_void_p(sums.data_ptr()), RTW_F32 if sums.dtype == torch.float32 else RTW_F64,
+                sums.numel() * sums.element_size(), C.c_void_p(features.data_ptr()), features.numel() * 8,
+                C.c_void_p(n.data_ptr()) if per_pixel else None, n.numel() * 4 if per_pixel else 0,
+                0 if per_pixel else int(n), W, H, C.byref(p), C.c_void_p(out.data_ptr()), out.numel() * 8,
+                C.c_void_p(stream) if stream else None), "rtw_denoise_device")
+            return out
+        s = np.ascontiguousarray(np.asarray(sums), np.float64)
+        if s.ndim != 3 or s.shape[2] != 3:
+            raise RenderError(_capi.RTW_E_INVALID, f"denoise: sums must be [H, W, 3], got {list(s.shape)}")
+        H, W = s.shape[:2]
+        f = np.ascontiguousarray(np.asarray(features), np.float64)
+        if f.shape != (H, W, 8):
+            raise RenderError(_capi.RTW_E_INVALID, f"denoise: features must be {[H, W, 8]}, got {list(f.shape)}")
+        cnt = _counts(n, H, W)
+        out = np.zeros((H, W, 3), np.float64)
+        self._check(_lib.rtw_denoise(self.ctx, s.ctypes.data_as(C.c_void_p), f.ctypes.data_as(C.c_void_p),
+                                     cnt.ctypes.data_as(C.c_void_p) if cnt is not None else None,
+                                     0 if cnt is not None else int(n), W, H, C.byref(p),
+                                     out.ctypes.data_as(C.c_void_p)), "rtw_denoise")
+        return out
+
+    def denoise_stats(self) -> "_capi.rtw_denoise_stats":
+        """Counters of the last denoise (rtw_get_denoise_stats; waits for it):
+        iterations, lds_iterations, filled, left_nonfinite, kernel_ms."""
+        st = _capi.rtw_denoise_stats()
+        self._check(_lib.rtw_get_denoise_stats(self.ctx, C.byref(st)), "rtw_get_denoise_stats")
+        return st
+
     def get_query_stats(self) -> "_capi.rtw_query_stats":
         """Counters of the last query (rtw_get_query_stats): rays, hits, node
         visits, sphere tests, light tests, the world / light path that ran."""
@@ -1150,6 +1223,28 @@ def write_ppm(path: str, sums: np.ndarray, spp) -> int:
     if n < 0:
         raise RenderError(n, f"cannot write {path}")
     return n
+
+
+class DenoiseParams:
+    """rtw_denoise_params: the library's defaults (rtw_denoise_params_default)
+    with the given fields replaced -- iterations (1..16), normal_power_log2
+    (0..10), sigma_colour (>= 0; 0: no colour weight), sigma_depth (> 0),
+    demodulate, fill_nonfinite (0 / 1).  The library checks the ranges."""
+    FIELDS = tuple(f for f, _ in _capi.rtw_denoise_params._fields_)
+
+    def __init__(self, **fields):
+        self.raw = _capi.rtw_denoise_params()
+        _lib.rtw_denoise_params_default(C.byref(self.raw))
+        for k, v in fields.items():
+            if k not in self.FIELDS:
+                raise RenderError(_capi.RTW_E_INVALID, f"DenoiseParams has no field {k!r} (it has {self.FIELDS})")
+            setattr(self.raw, k, float(v) if k.startswith("sigma") else int(v))
+
+    def __getattr__(self, name):
+        return getattr(self.__dict__["raw"], name)
+
+    def as_dict(self):
+        return {f: getattr(self.raw, f) for f in self.FIELDS}
 
 
 def feature_means(features, n):

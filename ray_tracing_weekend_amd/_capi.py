@@ -92,6 +92,21 @@ class rtw_query_stats(C.Structure):
     ]
 
 
+class rtw_denoise_params(C.Structure):
+    _fields_ = [
+        ("iterations", C.c_uint32), ("normal_power_log2", C.c_uint32),
+        ("sigma_colour", C.c_double), ("sigma_depth", C.c_double),
+        ("demodulate", C.c_uint32), ("fill_nonfinite", C.c_uint32),
+    ]
+
+
+class rtw_denoise_stats(C.Structure):
+    _fields_ = [
+        ("iterations", C.c_uint32), ("lds_iterations", C.c_uint32),
+        ("filled", C.c_uint64), ("left_nonfinite", C.c_uint64), ("kernel_ms", C.c_double),
+    ]
+
+
 # (name, restype, argtypes) for every entry point declared in include/rtw.h
 PROTOTYPES = [
     ("rtw_abi_version", C.c_int, []),
@@ -161,6 +176,13 @@ PROTOTYPES = [
     ("rtw_render_features_device", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32, C.c_uint32,
                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                              C.c_size_t, C.c_void_p]),
+    ("rtw_denoise_params_default", None, [C.POINTER(rtw_denoise_params)]),
+    ("rtw_denoise", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                              C.POINTER(rtw_denoise_params), C.c_void_p]),
+    ("rtw_denoise_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t,
+                                     C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
+                                     C.POINTER(rtw_denoise_params), C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("rtw_get_denoise_stats", C.c_int, [C.c_void_p, C.POINTER(rtw_denoise_stats)]),
     ("rtw_scene_simple", C.c_void_p, [C.c_uint64, C.c_int]),
     ("rtw_world_scene", C.POINTER(rtw_scene), [C.c_void_p]),
     ("rtw_world_camera_builder", None, [C.c_void_p, C.POINTER(rtw_camera_builder)]),

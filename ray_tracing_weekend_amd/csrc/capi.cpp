@@ -45,6 +45,7 @@ void rtw_destroy(rtw_ctx* c) {
     if (c->d_gather) (void)hipFree(c->d_gather);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     destroy_query(c);
+    destroy_denoise(c);
     if (c->d_scene) (void)hipFree(c->d_scene);
     if (c->d_partial) (void)hipFree(c->d_partial);
     if (c->d_accum) (void)hipFree(c->d_accum);
@@ -118,6 +119,7 @@ int rtw_set_tuning(rtw_ctx* c, const char* key, int64_t value) {
     else if (k == "balance") t.balance = value ? 1u : 0u;
     else if (k == "cost_time") t.cost_time = value ? 1u : 0u;
     else if (k == "tile_cull") t.tile_cull = value ? 1u : 0u;
+    else if (k == "denoise_lds") t.denoise_lds = (uint32_t)std::min<int64_t>(value, 2);
     else if (k == "guide_div") { t.guide_div = (uint32_t)std::min<int64_t>(value, 1 << 24); c->lpt.st.tab_valid = false; }
     else if (k == "guide_max") { t.guide_max = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 1), 4095); c->lpt.st.tab_valid = false; }
     else if (k == "guide_floor") { t.guide_floor = std::max<uint64_t>(1, (uint64_t)value); c->lpt.st.tab_valid = false; }

@@ -1,6 +1,6 @@
 // capi_ctx.hpp -- private to the C-ABI units (capi.cpp, capi_render.cpp,
 // capi_lpt.cpp, capi_adaptive.cpp, capi_multi.cpp, capi_query.cpp,
-// capi_features.cpp): the context behind include/rtw.h's rtw_ctx and the
+// capi_features.cpp, capi_denoise.cpp): the context behind include/rtw.h's rtw_ctx and the
 // helpers they share.
 #pragma once
 
@@ -106,6 +106,26 @@ struct QueryState {
     bool any = false;                 // a query was launched
 };
 
+// rtw_denoise (capi_denoise.cpp): the record arrays, the counters and events and
+// the host form's staging, allocated by the first denoise and grown on demand.
+struct DenoiseState {
+    void* d_records = nullptr;        // guide | albedo | colour 0 | colour 1 (host/denoise_plan.hpp)
+    size_t records_cap = 0;
+    unsigned long long* d_counters = nullptr;   // {filled, left non-finite}
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // the host form's staging: sums, features, counts in; the means out
+    void* d_sums = nullptr;
+    size_t sums_cap = 0;
+    void* d_features = nullptr;
+    size_t features_cap = 0;
+    void* d_counts = nullptr;
+    size_t counts_cap = 0;
+    void* d_out = nullptr;
+    size_t out_cap = 0;
+    rtw_denoise_stats last{};
+    bool any = false;                 // a denoise was launched
+};
+
 struct rtw_ctx {
     int device = 0;
     int precision = RTW_F32;
@@ -186,6 +206,8 @@ struct rtw_ctx {
     // batched ray queries and the feature pass: their own buffers, counters and events,
     // allocated by the first of them -- nothing of the render's is touched
     QueryState* query = nullptr;
+    // rtw_denoise: its own state as well, allocated by the first denoise
+    DenoiseState* denoise = nullptr;
 };
 
 static inline int fail(rtw_ctx* c, int code, const std::string& msg) {
@@ -304,3 +326,5 @@ void destroy_ranks(rtw_ctx* c);
 void destroy_query(rtw_ctx* c);
 // capi_query.cpp: the context's query state, allocated on first use
 int query_state(rtw_ctx* c);
+// capi_denoise.cpp: rtw_destroy's part for the denoise state (the context's device is current)
+void destroy_denoise(rtw_ctx* c);

@@ -4,12 +4,16 @@
 // writes image.ppm (P3, rows top to bottom).
 //
 //   rtw <scene> [--debug] [--seed N] [--f64] [--device N | --device-mask M] [--config PATH] [--out PATH]
-//       [--features PREFIX]
+//       [--features PREFIX] [--denoise PATH]
 //
 // --features PREFIX also writes the denoising guides of the render
 // (rtw_render_features, on one device): PREFIX_albedo.ppm, the albedo sums with
 // the sample count, and PREFIX_normal.ppm, (mean normal + 1) / 2 -- squared
 // before the writer's sqrt, so that the displayed value is linear.
+//
+// --denoise PATH also writes the denoised image (rtw_denoise over the render's
+// sums and its feature pass, with the default parameters); it implies the
+// feature pass and runs on one device like --features.
 //
 // <scene> is one of clap's ValueEnum names of main.rs:29-38 (cornell-box,
 // debug, checkered-spheres, perlin-spheres, plane, simple, simple-light,
@@ -59,7 +63,7 @@ bool read_config(const std::string& path, std::map<std::string, std::string>* kv
 }  // namespace
 
 int main(int argc, char** argv) {
-    std::string scene, config = "Config.toml", out = "image.ppm", features;
+    std::string scene, config = "Config.toml", out = "image.ppm", features, denoised;
     rtw::RenderOptions opt;
     for (int a = 1; a < argc; ++a) {
         std::string s = argv[a];
@@ -72,6 +76,7 @@ int main(int argc, char** argv) {
         else if (s == "--config" && a + 1 < argc) config = argv[++a];
         else if (s == "--out" && a + 1 < argc) out = argv[++a];
         else if (s == "--features" && a + 1 < argc) features = argv[++a];
+        else if (s == "--denoise" && a + 1 < argc) denoised = argv[++a];
         else if (scene.empty()) scene = s;
         else { fprintf(stderr, "unexpected argument %s\n", s.c_str()); return 2; }
     }
@@ -136,10 +141,21 @@ int main(int argc, char** argv) {
             fprintf(stderr, "cannot write %s\n", out.c_str());
             return 1;
         }
-        if (!features.empty()) {
+        if (!features.empty() || !denoised.empty()) {
             rtw::RenderOptions fopt = opt;
             fopt.device_mask = 0;   // the feature pass runs on one device
             const std::vector<double> f = cam.render_features(world, lights, 0, spp, {}, nullptr, fopt);
+            if (!denoised.empty()) {
+                rtw_denoise_stats st{};
+                const std::vector<double> mean = rtw::denoise(sums, f, {}, spp, W, H, nullptr, &st, fopt);
+                if (rtw_write_ppm(denoised.c_str(), mean.data(), W, H, 1) < 0) {
+                    fprintf(stderr, "cannot write %s\n", denoised.c_str());
+                    return 1;
+                }
+                fprintf(stderr, "denoise: %llu pixels filled, %llu left non-finite, %.3f ms\n",
+                        (unsigned long long)st.filled, (unsigned long long)st.left_nonfinite, st.kernel_ms);
+            }
+            if (features.empty()) return 0;
             std::vector<double> albedo((size_t)W * H * 3), normal((size_t)W * H * 3);
             for (size_t px = 0; px < (size_t)W * H; ++px) {
                 const double* v = &f[px * 8];

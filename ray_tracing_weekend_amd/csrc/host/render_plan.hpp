@@ -97,6 +97,8 @@ struct RenderKnobs {
                                       // than N samples per pixel run N at a time onto an f64
                                       // accumulator; kWindowAuto: the largest window whose chunk
                                       // sums fit partial_max
+    uint32_t denoise_lds = 1;         // rtw_denoise's iterations (host/denoise_plan.hpp): 0 all direct,
+                                      // 1 the plan's choice, 2 staged in LDS wherever the halo fits
 };
 
 // What plan_render decides.  err != RTW_OK: no render (err_text says why);

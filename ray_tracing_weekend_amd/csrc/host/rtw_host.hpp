@@ -290,6 +290,15 @@ std::vector<RayHit> hit_rays(const HittableList& world, const HittableList& ligh
 std::vector<double> light_pdf(const HittableList& world, const HittableList& lights, const std::vector<double>& rays,
                               const RenderOptions& opt = {});
 
+// The denoiser (rtw_denoise, include/rtw.h): the filtered per-sample means
+// [H][W][3] of the colour sums [H][W][3] and the feature sums [H][W][8] of
+// render_features, for the counts [H][W] -- empty: spp for every pixel.  params
+// null: the defaults.  No scene is staged; defined in host/denoise.cpp.
+std::vector<double> denoise(const std::vector<double>& sums, const std::vector<double>& features,
+                            const std::vector<uint32_t>& counts, uint32_t spp, uint32_t width, uint32_t height,
+                            const rtw_denoise_params* params = nullptr, rtw_denoise_stats* stats = nullptr,
+                            const RenderOptions& opt = {});
+
 namespace scenes {
 // scenes::simple restated with the build's seeded RNG; grid a, b in [-n, n).
 std::tuple<HittableList, HittableList, CameraBuilder> simple(uint64_t seed, int n = 11);
