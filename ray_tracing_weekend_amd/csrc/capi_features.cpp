@@ -1,10 +1,8 @@
 // capi_features.cpp -- the feature pass of the C-ABI (include/rtw.h):
 // rtw_render_features and its device form.  A pass is plan (host/query_plan.hpp,
-// with the camera's center) -> params -> launch -> bookkeeping, on the query
-// state's counters and events and its own staging buffers: nothing of the
-// render's or of a ray query's is touched.
-#include <math.h>
-
+// with the camera's center) -> params (feature_params) -> launch -> bookkeeping,
+// on the query state's counters and events and its own staging buffers: nothing
+// of the render's or of a ray query's is touched.
 #include <string>
 
 #include "capi_ctx.hpp"
@@ -35,32 +33,7 @@ int features_device_t(rtw_ctx* c, const rtw_camera& cam, uint64_t seed, uint32_t
     int rc = query_state(c);
     if (rc) return rc;
     QueryState* q = c->query;
-    rtw::FParams<R> p{};
-    p.sc = sc;
-    p.sc.robust = pl.robust;
-    for (int a = 0; a < 3; ++a) {   // the camera as a render's kernel sees it (pass_params)
-        p.center[a] = (R)cam.center[a];
-        p.p00[a] = (R)cam.pixel00_loc[a];
-        p.du[a] = (R)cam.pixel_delta_u[a];
-        p.dv[a] = (R)cam.pixel_delta_v[a];
-        p.disk_u[a] = (R)cam.defocus_disk_u[a];
-        p.disk_v[a] = (R)cam.defocus_disk_v[a];
-        p.bg[a] = (R)cam.background[a];
-    }
-    // Uniform::new_inclusive(-0.5, 0.5) scale (rand 0.8.6)
-    const double max_rand = 1.0 - 2.220446049250313080847e-16;
-    double scale = (0.5 - -0.5) / max_rand;
-    while (scale * max_rand + -0.5 > 0.5) scale = nextafter(scale, 0.0);
-    p.u_scale = (R)scale;
-    p.defocus = cam.defocus_angle > 2.220446049250313080847e-16 ? 1u : 0u;
-    p.seed = seed;
-    p.W = cam.image_width;
-    p.H = cam.image_height;
-    p.first = first;
-    p.end = first + n;
-    p.tiles_x = rtw::tiles_across(p.W);
-    p.n_tiles = p.tiles_x * rtw::tiles_across(p.H);
-    p.stack = pl.stack;
+    rtw::FParams<R> p = rtw::feature_params<R>(sc, cam, seed, first, n, pl);
     p.counts = d_counts;
     p.features = d_features;
     p.ids = first == 0 ? d_ids : nullptr;   // sample 0 is traced by a call that starts there

@@ -3,6 +3,9 @@
 
 #include <algorithm>
 
+#include "camera_params.hpp"
+#include "tiles.hpp"
+
 namespace rtw {
 
 template <typename R>
@@ -43,6 +46,28 @@ QueryPlan plan_query(const RenderKnobs& k, const DevScene<R>& sc, const SceneSca
     return q;
 }
 
+template <typename R>
+FParams<R> feature_params(const DevScene<R>& sc, const rtw_camera& cam, uint64_t seed, uint32_t first, uint32_t n,
+                          const QueryPlan& q) {
+    FParams<R> p{};
+    p.sc = sc;
+    p.sc.robust = q.robust;
+    fill_camera<R>(p, cam);
+    p.seed = seed;
+    p.W = cam.image_width;
+    p.H = cam.image_height;
+    p.first = first;
+    p.end = first + n;
+    p.tiles_x = tiles_across(p.W);
+    p.n_tiles = p.tiles_x * tiles_across(p.H);
+    p.stack = q.stack;
+    return p;
+}
+
+template FParams<float> feature_params<float>(const DevScene<float>&, const rtw_camera&, uint64_t, uint32_t, uint32_t,
+                                              const QueryPlan&);
+template FParams<double> feature_params<double>(const DevScene<double>&, const rtw_camera&, uint64_t, uint32_t,
+                                                uint32_t, const QueryPlan&);
 template QueryPlan plan_query<float>(const RenderKnobs&, const DevScene<float>&, const SceneScale&, const double*);
 template QueryPlan plan_query<double>(const RenderKnobs&, const DevScene<double>&, const SceneScale&, const double*);
 

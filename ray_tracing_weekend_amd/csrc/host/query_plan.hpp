@@ -3,10 +3,11 @@
 // dynamic LDS of hit_rays_kernel, and the light path of light_pdf_rays_kernel.
 // A query runs the traversal a render of the scene would run under the same
 // tuning keys: the world and the light path are render_plan.hpp plan_world's.
-// Host only, no HIP call.
+// The feature pass (rtw_render_features) runs on the same plan: its kernel
+// parameters are feature_params'.  Host only, no HIP call.
 #pragma once
 
-#include "../query_kernels.h"
+#include "../features_kernels.h"   // FParams, for feature_params (it includes query_kernels.h)
 #include "render_plan.hpp"
 
 namespace rtw {
@@ -30,5 +31,13 @@ struct QueryPlan {
 template <typename R>
 QueryPlan plan_query(const RenderKnobs& k, const DevScene<R>& sc, const SceneScale& scale,
                      const double* center = nullptr);
+
+// The kernel parameters of a feature pass planned as `q` (with the camera's
+// center): the scene, the camera as a render's kernel sees it (camera_params.hpp),
+// the samples [first, first + n) and the image's tiles.  The buffers (counts,
+// features, ids) and the counters are the caller's: null here.
+template <typename R>
+FParams<R> feature_params(const DevScene<R>& sc, const rtw_camera& cam, uint64_t seed, uint32_t first, uint32_t n,
+                          const QueryPlan& q);
 
 }  // namespace rtw

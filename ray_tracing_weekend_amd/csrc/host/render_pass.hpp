@@ -4,10 +4,9 @@
 // capi_render.cpp render_pass_t allocates, orders the tasks and launches.
 #pragma once
 
-#include <math.h>
-
 #include <algorithm>
 
+#include "camera_params.hpp"
 #include "render_plan.hpp"
 #include "tiles.hpp"
 
@@ -103,21 +102,7 @@ KParams<R> pass_params(const DevScene<R>& sc, const rtw_camera& cam, uint64_t se
     KParams<R> p{};
     p.sc = sc;
     p.sc.robust = pl.robust;
-    for (int a = 0; a < 3; ++a) {
-        p.center[a] = (R)cam.center[a];
-        p.p00[a] = (R)cam.pixel00_loc[a];
-        p.du[a] = (R)cam.pixel_delta_u[a];
-        p.dv[a] = (R)cam.pixel_delta_v[a];
-        p.disk_u[a] = (R)cam.defocus_disk_u[a];
-        p.disk_v[a] = (R)cam.defocus_disk_v[a];
-        p.bg[a] = (R)cam.background[a];
-    }
-    // Uniform::new_inclusive(-0.5, 0.5) scale (rand 0.8.6)
-    const double max_rand = 1.0 - 2.220446049250313080847e-16;
-    double scale = (0.5 - -0.5) / max_rand;
-    while (scale * max_rand + -0.5 > 0.5) scale = nextafter(scale, 0.0);
-    p.u_scale = (R)scale;
-    p.defocus = cam.defocus_angle > 2.220446049250313080847e-16 ? 1u : 0u;
+    fill_camera<R>(p, cam);
     p.seed = seed;
     p.W = cam.image_width;
     p.H = cam.image_height;

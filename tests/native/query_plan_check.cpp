@@ -17,7 +17,9 @@
 // Then a sweep of the tuning keys over the scenes: the query's world is
 // plan_render's for the same knobs, its LDS is within the device's and never
 // more than the render's for a tree in LDS, and every plan names kernels that
-// exist (query_kernels.h).
+// exist (query_kernels.h).  The feature pass's parameters (feature_params) are
+// held to the camera a render pass sees (render_pass.hpp pass_params), with
+// defocus and without.
 //
 // `query_plan_check kernels` only prints the kernel table, one
 // "hit <f32|f64> <world> <robust>" or "light <f32|f64> <path> <robust>" line each.
@@ -27,7 +29,9 @@
 
 #include <tuple>
 
+#include "host/camera_params.hpp"
 #include "host/query_plan.hpp"
+#include "host/render_pass.hpp"
 #include "host/rtw_host.hpp"
 #include "host/stage_scene.hpp"
 #include "host/tiles.hpp"
@@ -162,6 +166,40 @@ static void sweep(const char* name, const rtw_scene& s, const rtw_camera& cam, i
         }
 }
 
+// host/camera_params.hpp: a render pass (KParams of render_pass.hpp pass_params)
+// and a feature pass (FParams of feature_params) see the same camera, with
+// defocus and without
+template <typename R>
+static void check_camera_fill(const char* name, const rtw_camera& cam, const rtw::DevScene<R>& sc) {
+    // the two entry points: a render pass's parameters and a feature pass's
+    const rtw::KParams<R> k = rtw::pass_params<R>(sc, cam, 99, 0, 1, rtw::RenderKnobs(), rtw::RenderPlan(),
+                                                  rtw::one_shot_pass(cam));
+    rtw::QueryPlan q;
+    q.stack = 7;
+    q.robust = sizeof(R) == 4 ? 1u : 0u;
+    const rtw::FParams<R> f = rtw::feature_params<R>(sc, cam, 99, 3, 5, q);
+    const char* pr = sizeof(R) == 4 ? "f32" : "f64";
+    bool same = k.u_scale == f.u_scale && k.defocus == f.defocus;
+    for (int a = 0; a < 3; ++a)
+        same = same && k.center[a] == f.center[a] && k.p00[a] == f.p00[a] && k.du[a] == f.du[a] && k.dv[a] == f.dv[a] &&
+               k.disk_u[a] == f.disk_u[a] && k.disk_v[a] == f.disk_v[a] && k.bg[a] == f.bg[a];
+    CHECK(same, "%s %s: KParams and FParams differ in a camera field", name, pr);
+    CHECK(f.center[0] == (R)cam.center[0] && f.p00[1] == (R)cam.pixel00_loc[1] && f.du[0] == (R)cam.pixel_delta_u[0] &&
+              f.dv[1] == (R)cam.pixel_delta_v[1] && f.disk_u[0] == (R)cam.defocus_disk_u[0] &&
+              f.disk_v[1] == (R)cam.defocus_disk_v[1] && f.bg[2] == (R)cam.background[2],
+          "%s %s: a camera field is not the camera's", name, pr);
+    // Uniform::new_inclusive(-0.5, 0.5): the largest scale whose top sample stays <= 0.5
+    const double max_rand = 1.0 - 2.220446049250313080847e-16;
+    CHECK((double)f.u_scale * max_rand + -0.5 <= 0.5 && f.u_scale >= (R)1 && f.u_scale <= (R)(1.0 + 1e-6),
+          "%s %s: u_scale %.17g", name, pr, (double)f.u_scale);
+    CHECK(f.defocus == (cam.defocus_angle > 2.220446049250313080847e-16 ? 1u : 0u), "%s %s: defocus %u", name, pr,
+          f.defocus);
+    CHECK(f.seed == 99 && f.W == cam.image_width && f.H == cam.image_height && f.first == 3 && f.end == 8 &&
+              f.tiles_x == rtw::tiles_across(f.W) && f.n_tiles == f.tiles_x * rtw::tiles_across(f.H) && f.stack == 7 &&
+              f.sc.robust == q.robust && f.sc.n_sph == sc.n_sph && !f.counts && !f.features && !f.ids && !f.counters,
+          "%s %s: the pass's own fields", name, pr);
+}
+
 static int print_kernels() {
     int n = 0;
     for (int f64 = 0; f64 < 2; ++f64)
@@ -281,6 +319,21 @@ int main(int argc, char** argv) {
         a.ds.bvh_depth = rtw::kBvhStack + 1;
         const rtw::QueryPlan q = rtw::plan_query<float>(k, a.ds, a.scale);
         CHECK(q.err == RTW_E_UNSUPPORTED, "deep BVH: error %d '%s'", q.err, q.err_text);
+    }
+    {
+        rtw::CameraBuilder b = std::get<2>(simple_t);
+        const rtw_camera sharp = small_camera(b.with_defocus_angle(0.0));
+        const rtw_camera blurred = small_camera(b.with_defocus_angle(0.6).with_focus_dist(10.0));
+        CHECK(sharp.defocus_angle == 0.0 && blurred.defocus_angle > 0.0 &&
+                  (blurred.defocus_disk_u[0] != 0.0 || blurred.defocus_disk_u[1] != 0.0 || blurred.defocus_disk_u[2] != 0.0),
+              "the two cameras: one without defocus, one with a defocus disk");
+        const rtw::RenderKnobs k;
+        const Staged<float> a = stage<float>(simple, k);
+        const Staged<double> b64 = stage<double>(simple, k);
+        check_camera_fill<float>("sharp", sharp, a.ds);
+        check_camera_fill<double>("sharp", sharp, b64.ds);
+        check_camera_fill<float>("defocus", blurred, a.ds);
+        check_camera_fill<double>("defocus", blurred, b64.ds);
     }
     {
         int n_plans = 0;
