@@ -582,8 +582,9 @@ int rtw_last_kernel(const rtw_ctx *ctx);
  * uses (entities/transformations.rs:14-29): the world-space point with the
  * object-space normal, front face and UV.
  * t_min: one scalar per call, finite and >= 0 (the reference passes
- * f64::EPSILON from the integrator, 0 from pdf_value); the upper end is
- * always +inf, the only one the reference passes.
+ * f64::EPSILON from the integrator, 0 from pdf_value); the upper end of the
+ * closest-hit query is always +inf, the only one the reference's integrator
+ * passes -- a ranged any-hit is rtw_occluded_rays below.
  *
  * Errors: RTW_E_INVALID for a NULL context, a NULL array with n > 0, a buffer
  * that is too small, a negative / NaN / infinite t_min; RTW_E_NO_SCENE before
@@ -611,11 +612,78 @@ typedef struct rtw_query_stats {
     uint32_t kernel;              /* closest hit: the world that ran, as rtw_stats.kernel;
                                      light pdf: 0 linear list, 1 light BVH, 2 light grid,
                                      3 mixed list (quads / default entries) */
-    uint32_t is_light_pdf;        /* 1: the last query was a light pdf */
+    uint32_t is_light_pdf;        /* the last query: 0 closest hit (or a feature pass), 1 light
+                                     pdf, 2 any hit (rtw_occluded_rays: `hits` counts the
+                                     occluded rays, `kernel` is the world), 3 light sample
+                                     (rtw_light_sample: `kernel` is the light path,
+                                     light_tests those of the fused pdf) */
     double kernel_ms;             /* device time of the query kernel (HIP events) */
 } rtw_query_stats;
 /* Counters of the last query (waits for it); RTW_E_INVALID before the first. */
 int rtw_get_query_stats(rtw_ctx *ctx, rtw_query_stats *stats);
+
+/* ---- any-hit occlusion and light sampling: what an outside integrator needs -
+ * With the light pdf above these answer the Hittable trait completely (hit
+ * with a range, pdf_value, random): per shading point a direction towards a
+ * light, its pdf, and a shadow ray.  Both run on the plan of the queries above
+ * (the same world, test form, stack, LDS and light path under the same tuning
+ * keys), through the same device functions, on the queries' own buffers.
+ *
+ * rtw_occluded_rays: world.hit(&r, t_min..=t_max[i]).is_some() for n rays
+ * (hittable_list.rs:395-406, bvh.rs:164-188) -- the reference's semantics, not
+ * a closest hit with a smaller bound:
+ *   - a candidate is accepted when t_min <= t && t <= t_max, inclusive at both
+ *     ends (RangeInclusive); per primitive, t is the closest-hit query's t bit
+ *     for bit in each precision;
+ *   - a sphere whose near root is outside the range is tried at its far root
+ *     (sphere.rs:72-80);
+ *   - the range is not shrunk from object to object (hittable_list.rs:399-405);
+ *   - the AABB gates of planes, quads and cuboids (bounded_hit, hittable.rs:
+ *     39-86) test max(t_min, tn) <= min(t_max, tf): a finite t_max is part of
+ *     the gate.  Spheres are tested without a gate of their own: as in the
+ *     closest-hit query, neither the sweep nor the BVH leaves model a sphere's
+ *     unpadded box (the sphere's own root test decides).
+ * The traversal stops at the first accepted hit: a ray blocked by a plane, quad
+ * or cuboid never enters the sphere traversal, and an accepted sphere culls
+ * every box still on the ray's stack.
+ *   rays    : n x 6, as rtw_hit_rays
+ *   t_max   : n values of the context's precision, or NULL for +inf.  +inf is
+ *             allowed; t_max[i] NaN or < t_min answers 0.  A NaN ray answers 0.
+ *   occluded: n bytes, 0 or 1
+ * t_min and the errors are rtw_hit_rays'.  Query stats: is_light_pdf = 2, hits =
+ * the occluded rays, kernel = the world that ran.
+ *
+ * rtw_light_sample: lights.random(origin, rng) (hittable_list.rs:414-419) for n
+ * points and, when pdf is not NULL, lights.pdf_value(origin, direction drawn).
+ * The stream convention for points that belong to no pixel: point k draws from
+ * the stream a render gives to (seed, pixel index first_stream + k, sample
+ * index `sample`) -- the keying of the render's RNG (splitmix64 over seed,
+ * pixel + 1, sample + 1 into xoshiro256++), with a 64-bit pixel index -- and
+ * makes from its start exactly the draws the render's Lambertian branch makes
+ * for lights.random: one gen_range(0..len) for the entry, then the entry's
+ * random() (Sphere::random sphere.rs:114-127, Quad::random quadrilateral.rs:
+ * 114-118, the (1, 0, 0) default of hittable.rs).  Calls compose: (first_stream
+ * = a, n) followed by (a + n, m) equals one call of n + m points.
+ *   origins   : n x 3 in the context's precision
+ *   directions: n x 3 as the reference returns them: unnormalised; for a quad
+ *               p - origin, so a shadow ray along one has t_max just under 1;
+ *               an origin inside a sphere light gives the reference's NaN
+ *   pdf       : n values or NULL; rtw_light_pdf_rays of {origin, direction} bit
+ *               for bit (the same light path: linear, light BVH, grid, mixed;
+ *               the RTW_LIGHTS_BVH_LEAF form included)
+ *   light     : n list indices (the entry drawn), or NULL
+ * An empty light list is RTW_E_INVALID (the reference panics, hittable_list.rs:
+ * 417); the other errors are the queries'.  Query stats: is_light_pdf = 3,
+ * kernel = the light path, light_tests those of the fused pdf. */
+int rtw_occluded_rays(rtw_ctx *ctx, const void *rays, uint64_t n, double t_min, const void *t_max,
+                      uint8_t *occluded);
+int rtw_occluded_rays_device(rtw_ctx *ctx, const void *d_rays, uint64_t n, double t_min, const void *d_t_max,
+                             size_t t_max_bytes, uint8_t *d_occluded, size_t occluded_bytes, void *stream);
+int rtw_light_sample(rtw_ctx *ctx, const void *origins, uint64_t n, uint64_t seed, uint64_t first_stream,
+                     uint32_t sample, void *directions, void *pdf, int32_t *light);
+int rtw_light_sample_device(rtw_ctx *ctx, const void *d_origins, uint64_t n, uint64_t seed, uint64_t first_stream,
+                            uint32_t sample, void *d_directions, size_t directions_bytes, void *d_pdf,
+                            size_t pdf_bytes, int32_t *d_light, size_t light_bytes, void *stream);
 
 /* ---- feature buffers for denoisers: first-hit albedo, normal, distance ----
  * One fused pass over the render's own primary rays.  For pixel (i, j) and the

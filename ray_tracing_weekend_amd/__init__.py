@@ -229,6 +229,25 @@ class HittableList:                          # hittable_collections/hittable_lis
             r.set_scene(flatten(world if world is not None else HittableList(), self))
             return r.light_pdf(rays)
 
+    def occluded(self, rays, t_max=None, t_min: float | None = None, *, lights=None, precision: int = RTW_F64,
+                 device: int = 0, accel: int = RTW_ACCEL_AUTO):
+        """Hittable::hit of this list as the world over t_min..=t_max[i],
+        .is_some(): uint8 [n] as Renderer.occluded gives them."""
+        with Renderer(device=device, precision=precision) as r:
+            r.set_accel(accel)
+            r.set_scene(flatten(self, lights if lights is not None else HittableList()))
+            return r.occluded(rays, t_max, t_min)
+
+    def random(self, origins, seed: int, first_stream: int = 0, sample: int = 0, *, pdf: bool = True, world=None,
+               precision: int = RTW_F64, device: int = 0, accel: int = RTW_ACCEL_AUTO):
+        """HittableList::random of this list as the light list
+        (hittable_list.rs:414-419) for n origins [n, 3]: (directions, pdf or
+        None, light) as Renderer.light_sample gives them."""
+        with Renderer(device=device, precision=precision) as r:
+            r.set_accel(accel)
+            r.set_scene(flatten(world if world is not None else HittableList(), self))
+            return r.light_sample(origins, seed, first_stream, sample, pdf)
+
 
 class BoundedVolumeHierarchy(HittableList):  # hittable_collections/bvh.rs:106-143 (::from(list))
     """The reference's BVH over a list: as the world it gives the list's
@@ -896,6 +915,92 @@ class Renderer:
         self._check(_lib.rtw_light_pdf_rays(self.ctx, r.ctypes.data_as(C.c_void_p), n,
                                             pdf.ctypes.data_as(C.c_void_p)), "rtw_light_pdf_rays")
         return pdf
+
+    # ---- any-hit occlusion and light sampling (rtw_occluded_rays / rtw_light_sample)
+    def occluded(self, rays, t_max=None, t_min: float | None = None):
+        """world.hit(&r, t_min..=t_max[i]).is_some() of the staged scene for n
+        rays [n, 6]: uint8 [n], 1 where anything lies in the inclusive range.
+        t_max: [n] of the context's precision, or None for +inf; an entry that
+        is NaN or below t_min answers 0, as does a NaN ray.  t_min defaults to
+        f64::EPSILON.  The traversal stops at the first accepted hit.  numpy /
+        torch as hit_rays (a torch t_max must be a tensor like the rays)."""
+        t_min = 2.220446049250313e-16 if t_min is None else float(t_min)
+        r, is_torch = self._query_rays(rays, "occluded")
+        n = int(r.shape[0])
+        if is_torch:
+            import torch
+            if t_max is not None:
+                if type(t_max).__module__.split(".")[0] != "torch" or t_max.dtype != r.dtype or \
+                        t_max.device != r.device or t_max.dim() != 1 or t_max.shape[0] != n or \
+                        not t_max.is_contiguous():
+                    raise RenderError(_capi.RTW_E_INVALID, "occluded: t_max must be a contiguous [n] tensor of the "
+                                                           "rays' dtype and device")
+            occ = torch.zeros((n,), dtype=torch.uint8, device=r.device)
+            stream = _torch_stream(self.device)
+            self._check(_lib.rtw_occluded_rays_device(
+                self.ctx, C.c_void_p(r.data_ptr()), n, t_min,
+                C.c_void_p(t_max.data_ptr()) if t_max is not None and n else None,
+                t_max.numel() * t_max.element_size() if t_max is not None else 0,
+                C.c_void_p(occ.data_ptr()), occ.numel(), C.c_void_p(stream) if stream else None),
+                "rtw_occluded_rays_device")
+            return occ
+        tm = None
+        if t_max is not None:
+            tm = np.ascontiguousarray(np.asarray(t_max, r.dtype))
+            if tm.shape != (n,):
+                raise RenderError(_capi.RTW_E_INVALID, "occluded: t_max must be [n], one upper end per ray")
+        occ = np.zeros(n, np.uint8)
+        self._check(_lib.rtw_occluded_rays(self.ctx, r.ctypes.data_as(C.c_void_p), n, t_min,
+                                           tm.ctypes.data_as(C.c_void_p) if tm is not None and n else None,
+                                           occ.ctypes.data_as(C.c_void_p)), "rtw_occluded_rays")
+        return occ
+
+    def light_sample(self, origins, seed: int, first_stream: int = 0, sample: int = 0, pdf: bool = True):
+        """lights.random(origin, rng) of the staged light list for n points
+        [n, 3]: (directions [n, 3], pdf [n] or None, light [n] int32).  Point k
+        draws from the stream a render gives to (seed, pixel first_stream + k,
+        sample): one index draw, then the entry's random() -- so calls compose
+        over first_stream.  Directions are the reference's, unnormalised (a
+        quad's is p - origin; NaN for an origin inside a sphere light); pdf is
+        light_pdf of {origin, direction} bit for bit, fused into the same
+        kernel; light is the list index drawn.  An empty light list is
+        refused.  numpy / torch as hit_rays."""
+        np_dtype = np.float32 if self.precision == RTW_F32 else np.float64
+        is_torch = type(origins).__module__.split(".")[0] == "torch"
+        seed, first_stream, sample = int(seed), int(first_stream), int(sample)
+        if is_torch:
+            import torch
+            want = torch.float32 if self.precision == RTW_F32 else torch.float64
+            if origins.dtype != want:
+                raise RenderError(_capi.RTW_E_INVALID, f"light_sample: tensor dtype {origins.dtype}, the context's is {want}")
+            if not origins.is_cuda or origins.device.index != self.device:
+                raise RenderError(_capi.RTW_E_INVALID, f"light_sample: the tensor is not on device {self.device}")
+            if origins.dim() != 2 or origins.shape[1] != 3 or not origins.is_contiguous():
+                raise RenderError(_capi.RTW_E_INVALID, "light_sample: origins must be a contiguous [n, 3] tensor")
+            n = int(origins.shape[0])
+            dirs = torch.zeros((n, 3), dtype=want, device=origins.device)
+            p = torch.zeros((n,), dtype=want, device=origins.device) if pdf else None
+            light = torch.zeros((n,), dtype=torch.int32, device=origins.device)
+            stream = _torch_stream(self.device)
+            self._check(_lib.rtw_light_sample_device(
+                self.ctx, C.c_void_p(origins.data_ptr()), n, seed, first_stream, sample,
+                C.c_void_p(dirs.data_ptr()), dirs.numel() * dirs.element_size(),
+                C.c_void_p(p.data_ptr()) if pdf and n else None, p.numel() * p.element_size() if pdf else 0,
+                C.c_void_p(light.data_ptr()), light.numel() * 4, C.c_void_p(stream) if stream else None),
+                "rtw_light_sample_device")
+            return dirs, p, light
+        o = np.ascontiguousarray(np.asarray(origins, np_dtype))
+        if o.ndim != 2 or o.shape[1] != 3:
+            raise RenderError(_capi.RTW_E_INVALID, "light_sample: origins must be [n, 3]")
+        n = int(o.shape[0])
+        dirs = np.zeros((n, 3), np_dtype)
+        p = np.zeros(n, np_dtype) if pdf else None
+        light = np.zeros(n, np.int32)
+        self._check(_lib.rtw_light_sample(self.ctx, o.ctypes.data_as(C.c_void_p), n, seed, first_stream, sample,
+                                          dirs.ctypes.data_as(C.c_void_p),
+                                          p.ctypes.data_as(C.c_void_p) if pdf and n else None,
+                                          light.ctypes.data_as(C.c_void_p)), "rtw_light_sample")
+        return dirs, p, light
 
     # ---- feature buffers for denoisers (rtw_render_features)
     def render_features(self, cam: Camera, seed: int, first: int = 0, n: int | None = None, *, counts=None,

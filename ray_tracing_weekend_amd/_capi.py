@@ -171,6 +171,14 @@ PROTOTYPES = [
     ("rtw_light_pdf_rays_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t,
                                             C.c_void_p]),
     ("rtw_get_query_stats", C.c_int, [C.c_void_p, C.POINTER(rtw_query_stats)]),
+    ("rtw_occluded_rays", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_double, C.c_void_p, C.c_void_p]),
+    ("rtw_occluded_rays_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_double, C.c_void_p, C.c_size_t,
+                                           C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("rtw_light_sample", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rtw_light_sample_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                          C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                          C.c_void_p]),
     ("rtw_render_features", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32, C.c_uint32,
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rtw_render_features_device", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32, C.c_uint32,

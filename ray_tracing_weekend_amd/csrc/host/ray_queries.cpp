@@ -62,4 +62,32 @@ std::vector<double> light_pdf(const HittableList& world, const HittableList& lig
     return pdf;
 }
 
+std::vector<uint8_t> occluded(const HittableList& world, const HittableList& lights, const std::vector<double>& rays,
+                              const std::vector<double>& t_max, double t_min, const RenderOptions& opt) {
+    if (rays.size() % 6) throw Error(RTW_E_INVALID, "occluded: rays holds 6 values per ray");
+    const size_t n = rays.size() / 6;
+    if (!t_max.empty() && t_max.size() != n) throw Error(RTW_E_INVALID, "occluded: t_max holds one value per ray");
+    std::vector<uint8_t> occ(n);
+    rtw_ctx* ctx = query_context(world, lights, opt);
+    finish(ctx, rtw_occluded_rays(ctx, rays.data(), n, t_min, t_max.empty() ? nullptr : t_max.data(), occ.data()),
+           "rtw_occluded_rays");
+    return occ;
+}
+
+LightSamples light_sample(const HittableList& world, const HittableList& lights, const std::vector<double>& origins,
+                          uint64_t seed, uint64_t first_stream, uint32_t sample, bool with_pdf,
+                          const RenderOptions& opt) {
+    if (origins.size() % 3) throw Error(RTW_E_INVALID, "light_sample: origins holds 3 values per point");
+    const size_t n = origins.size() / 3;
+    LightSamples out;
+    out.directions.resize(3 * n);
+    if (with_pdf) out.pdf.resize(n);
+    out.light.resize(n);
+    rtw_ctx* ctx = query_context(world, lights, opt);
+    finish(ctx, rtw_light_sample(ctx, origins.data(), n, seed, first_stream, sample, out.directions.data(),
+                                 with_pdf ? out.pdf.data() : nullptr, out.light.data()),
+           "rtw_light_sample");
+    return out;
+}
+
 }  // namespace rtw

@@ -289,6 +289,22 @@ std::vector<RayHit> hit_rays(const HittableList& world, const HittableList& ligh
 // lights.pdf_value(origin, direction) per ray (hittable_list.rs:408-412)
 std::vector<double> light_pdf(const HittableList& world, const HittableList& lights, const std::vector<double>& rays,
                               const RenderOptions& opt = {});
+// world.hit(&r, t_min..=t_max[k]).is_some() per ray (rtw_occluded_rays): 0 / 1.
+// t_max: one upper end per ray, or empty for +inf.
+std::vector<uint8_t> occluded(const HittableList& world, const HittableList& lights, const std::vector<double>& rays,
+                              const std::vector<double>& t_max = {}, double t_min = 2.220446049250313e-16,
+                              const RenderOptions& opt = {});
+// lights.random(origin, rng) per origin (3 values each; rtw_light_sample): point k
+// draws from the stream of (seed, pixel first_stream + k, sample).  pdf (when
+// with_pdf) is light_pdf of {origin, direction}; light the list index drawn.
+struct LightSamples {
+    std::vector<double> directions;   // 3 per origin, unnormalised
+    std::vector<double> pdf;          // 1 per origin, or empty
+    std::vector<int32_t> light;
+};
+LightSamples light_sample(const HittableList& world, const HittableList& lights, const std::vector<double>& origins,
+                          uint64_t seed, uint64_t first_stream = 0, uint32_t sample = 0, bool with_pdf = true,
+                          const RenderOptions& opt = {});
 
 // The denoiser (rtw_denoise, include/rtw.h): the filtered per-sample means
 // [H][W][3] of the colour sums [H][W][3] and the feature sums [H][W][8] of
