@@ -616,7 +616,9 @@ typedef struct rtw_query_stats {
                                      pdf, 2 any hit (rtw_occluded_rays: `hits` counts the
                                      occluded rays, `kernel` is the world), 3 light sample
                                      (rtw_light_sample: `kernel` is the light path,
-                                     light_tests those of the fused pdf) */
+                                     light_tests those of the fused pdf), 4 camera rays
+                                     (rtw_camera_rays), 5 the bounce (rtw_shade_rays: `hits`
+                                     counts the rays that continue, `kernel` is the light path) */
     double kernel_ms;             /* device time of the query kernel (HIP events) */
 } rtw_query_stats;
 /* Counters of the last query (waits for it); RTW_E_INVALID before the first. */
@@ -684,6 +686,116 @@ int rtw_light_sample(rtw_ctx *ctx, const void *origins, uint64_t n, uint64_t see
 int rtw_light_sample_device(rtw_ctx *ctx, const void *d_origins, uint64_t n, uint64_t seed, uint64_t first_stream,
                             uint32_t sample, void *d_directions, size_t directions_bytes, void *d_pdf,
                             size_t pdf_bytes, int32_t *d_light, size_t light_bytes, void *stream);
+
+/* ---- path queries: camera rays and the material bounce ---------------------
+ * The Material trait (shared/src/material.rs:32-49) and Camera::get_ray as
+ * batched queries, linked by the RNG state they return.  With rtw_hit_rays
+ * between them a caller's loop is a wavefront path tracer:
+ *     rays, rng = camera_rays(sample s)        mult = 1, res = 0
+ *     repeat max_depth times:  hits, ids = hit_rays(rays, t_min = f64::EPSILON)
+ *                              next, weight, emitted, event = shade_rays(...)
+ *     MISS     colour = mult * background + res                (camera.rs:473-475)
+ *     ABSORBED colour = mult * emitted + res                   (camera.rs:484-486)
+ *     REFLECT  mult *= weight                                  (camera.rs:488-500)
+ *     SCATTER  res += mult * emitted, then mult *= weight      (camera.rs:504-521)
+ *     paths still alive after max_depth rounds: colour = 0 + res (camera.rs:470-472)
+ * In RTW_F64 the image of that loop is bit for bit Camera::render's.
+ *
+ * rtw_camera_rays: Camera::get_ray (camera.rs:274-293) for n pixels and one
+ * sample index.  Ray k belongs to pixel index pixels[k], or first_pixel + k
+ * when pixels is NULL; the index is j * image_width + i, the render's stream
+ * key (j = 0 is the bottom row).  The stream is the one a render gives to
+ * (seed, that pixel, sample): splitmix64 over seed, pixel + 1, sample + 1 into
+ * xoshiro256++.  From its start the call makes exactly get_ray's draws:
+ *   1. Uniform::new_inclusive(-0.5, 0.5) for the x offset (camera.rs:275-276),
+ *   2. Uniform::new_inclusive(-0.5, 0.5) for the y offset (camera.rs:276),
+ *   3. only when defocus_angle > f64::EPSILON: the UnitDisk rejection loop
+ *      (utils.rs:124-144), two Standard draws per try (camera.rs:285-290).
+ *   rays: n x 6 {origin, direction = pixel sample - origin} in the context's
+ *         precision, the direction unnormalised
+ *   rng : n x 4 uint64, the xoshiro256++ words s0..s3 after those draws
+ * cam->samples_per_pixel and max_depth are not read.  No scene needs to be
+ * staged.  An index >= image_width * image_height is RTW_E_INVALID: the host
+ * form checks every index; for the device form an out-of-range entry of
+ * d_pixels is the caller's error -- it is clamped to the last pixel, so nothing
+ * is read or written out of bounds.  Query stats: is_light_pdf = 4.
+ *
+ * rtw_shade_rays: one iteration of ray_colour_tail_call after world.hit
+ * (camera.rs:480-521) for n rays.  rays are the incoming rays, hits and ids
+ * exactly what rtw_hit_rays wrote for them.  The kernel reads no world
+ * geometry: the record, the material and texture tables and the light list.
+ *   event  : n int32
+ *     RTW_EVENT_MISS      object id < 0.  Every output row is 0 and the ray's
+ *                         rng is left untouched.
+ *     RTW_EVENT_ABSORBED  scatter() is None: DiffuseLight (material.rs:490-514),
+ *                         Invisible (material.rs:321-325), a Metal direction with
+ *                         !(dot(direction, normal) > 0) (material.rs:416).
+ *                         next, weight and pdfs are 0.
+ *     RTW_EVENT_REFLECT   Metal or Dialectric (ScatterRecord::Reflect).
+ *     RTW_EVENT_SCATTER   Lambertian (ScatterRecord::Scatter).
+ *   emitted: n x 3, Material::emitted(u, v, p) with the texture evaluated at
+ *            the record's (u, v, p) (material.rs:508-514; black otherwise,
+ *            material.rs:42-44)
+ *   weight : n x 3: Metal's albedo; (1, 1, 1) for Dialectric; for Lambertian
+ *            (attenuation * scattering_pdf) / pdf_value in that association
+ *            (camera.rs:518)
+ *   next   : n x 6 {p, direction}, the direction as the reference returns it,
+ *            unnormalised
+ *   pdfs   : n x 3 or NULL: {MixturePdf value (pdf.rs:90-92), the light list's
+ *            pdf_value (hittable_list.rs:408-412; the RTW_LIGHTS_BVH_LEAF form
+ *            bvh.rs:67-76), scattering_pdf (material.rs:372-375)}; 0 unless the
+ *            event is SCATTER.  The light list's value is rtw_light_pdf_rays of
+ *            {p, direction} bit for bit: the same light path (linear, light BVH,
+ *            grid, mixed) under the same tuning keys, through the same code.
+ *   rng    : n x 4 uint64, required; read, advanced by exactly the draws of
+ *            the reference's branch and written back:
+ *     Metal       the UnitSphere rejection loop (utils.rs:99-122), three
+ *                 Standard draws per try (material.rs:415); RTW_F32 draws three
+ *                 words in all (the speed mode's direct sampler)
+ *     Dialectric  one Open01, only when refraction is possible
+ *                 (material.rs:474-476: not drawn on total internal reflection)
+ *     Lambertian  one Standard for the lobe (pdf.rs:95); below 0.5
+ *                 gen_range(0..len) and the entry's random()
+ *                 (hittable_list.rs:414-419: Sphere two Standard, Quad two
+ *                 Open01, the Hittable default none), else the cosine
+ *                 hemisphere's two Standard (utils.rs:146-161)
+ *     DiffuseLight, Invisible   nothing
+ *            Four zero words are no xoshiro256++ state (no seeding produces them;
+ *            every draw would be 0 and a rejection loop would never end): such a
+ *            row draws from the stream of (seed 0, pixel 0, sample 0) instead.
+ * A row whose material id is not one of the scene's is answered as a MISS.
+ * RTW_F64: every output bit is the reference's.  RTW_F32: the plain f32
+ * arithmetic of the speed mode; a loop of plain-f32 queries is not the hit64
+ * render (whose hit points are refined in f64) and is outside the f32
+ * tolerance of the renders.
+ * Errors are the queries': RTW_E_INVALID for a NULL context, a NULL array with
+ * n > 0 (pdfs excepted) or a buffer that is too small or, in the device forms,
+ * not aligned for its records -- the largest power of two that divides the
+ * record's size, 16 at the most: rays and next 16 bytes in RTW_F64 and 8 in
+ * RTW_F32, hits / weight / emitted / pdfs 8 and 4, ids and rng 16, event 4 (so
+ * a row slice of any of them is as good as the whole array); RTW_E_NO_SCENE before rtw_set_scene (rtw_shade_rays);
+ * RTW_E_UNSUPPORTED on a multi-device or virtual-rank context; n = 0 launches
+ * nothing.  The one difference from the render: an empty light list in a scene
+ * that holds a Lambertian material is refused with RTW_E_NO_LIGHTS before the
+ * launch (the reference panics, hittable_list.rs:417; the render carries a NaN
+ * on).  Query stats: is_light_pdf = 5, hits = the rays that continue (REFLECT +
+ * SCATTER), light_tests those of the fused light pdf, kernel = the light path. */
+#define RTW_EVENT_MISS 0
+#define RTW_EVENT_ABSORBED 1
+#define RTW_EVENT_REFLECT 2
+#define RTW_EVENT_SCATTER 3
+int rtw_camera_rays(rtw_ctx *ctx, const rtw_camera *cam, uint64_t seed, uint32_t sample, const uint32_t *pixels,
+                    uint64_t first_pixel, uint64_t n, void *rays, uint64_t *rng);
+int rtw_camera_rays_device(rtw_ctx *ctx, const rtw_camera *cam, uint64_t seed, uint32_t sample,
+                           const uint32_t *d_pixels, size_t pixels_bytes, uint64_t first_pixel, uint64_t n,
+                           void *d_rays, size_t rays_bytes, uint64_t *d_rng, size_t rng_bytes, void *stream);
+int rtw_shade_rays(rtw_ctx *ctx, const void *rays, const void *hits, const int32_t *ids, uint64_t n, uint64_t *rng,
+                   void *next, void *weight, void *emitted, int32_t *event, void *pdfs);
+int rtw_shade_rays_device(rtw_ctx *ctx, const void *d_rays, size_t rays_bytes, const void *d_hits, size_t hits_bytes,
+                          const int32_t *d_ids, size_t ids_bytes, uint64_t n, uint64_t *d_rng, size_t rng_bytes,
+                          void *d_next, size_t next_bytes, void *d_weight, size_t weight_bytes, void *d_emitted,
+                          size_t emitted_bytes, int32_t *d_event, size_t event_bytes, void *d_pdfs, size_t pdfs_bytes,
+                          void *stream);
 
 /* ---- feature buffers for denoisers: first-hit albedo, normal, distance ----
  * One fused pass over the render's own primary rays.  For pixel (i, j) and the

@@ -82,6 +82,7 @@ class rtw_stats(C.Structure):
 
 
 RTW_PRIM_PLANE, RTW_PRIM_QUAD, RTW_PRIM_CUBOID, RTW_PRIM_SPHERE = 0, 1, 2, 3
+RTW_EVENT_MISS, RTW_EVENT_ABSORBED, RTW_EVENT_REFLECT, RTW_EVENT_SCATTER = 0, 1, 2, 3
 
 
 class rtw_query_stats(C.Structure):
@@ -179,6 +180,17 @@ PROTOTYPES = [
     ("rtw_light_sample_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
                                           C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                           C.c_void_p]),
+    ("rtw_camera_rays", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64,
+                                  C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("rtw_camera_rays_device", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32, C.c_void_p,
+                                         C.c_size_t, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p,
+                                         C.c_size_t, C.c_void_p]),
+    ("rtw_shade_rays", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rtw_shade_rays_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                        C.c_size_t, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                        C.c_void_p, C.c_size_t, C.c_void_p]),
     ("rtw_render_features", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32, C.c_uint32,
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rtw_render_features_device", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32, C.c_uint32,

@@ -220,6 +220,8 @@ int rtw_set_scene(rtw_ctx* c, const rtw_scene* s) {
             return k ? fail(c, rc, ck->err) : rc;
         }
     }
+    c->has_lambertian = false;
+    for (uint32_t m = 0; m < s->n_materials; ++m) c->has_lambertian |= s->mat_type[m] == RTW_LAMBERTIAN;
     if (!c->peers.empty()) HIP_TRY(c, hipSetDevice(c->device));
     return RTW_OK;
 }

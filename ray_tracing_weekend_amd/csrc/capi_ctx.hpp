@@ -1,6 +1,6 @@
 // capi_ctx.hpp -- private to the C-ABI units (capi.cpp, capi_render.cpp,
-// capi_lpt.cpp, capi_adaptive.cpp, capi_multi.cpp, capi_query.cpp,
-// capi_features.cpp, capi_denoise.cpp): the context behind include/rtw.h's rtw_ctx and the
+// capi_lpt.cpp, capi_adaptive.cpp, capi_multi.cpp, capi_query.cpp, capi_nee.cpp,
+// capi_path.cpp, capi_features.cpp, capi_denoise.cpp): the context behind include/rtw.h's rtw_ctx and the
 // helpers they share.
 #pragma once
 
@@ -145,6 +145,7 @@ struct rtw_ctx {
     rtw::DevScene<float> sc32{};
     rtw::DevScene<double> sc64{};
     bool has_scene = false;
+    bool has_lambertian = false;      // the staged scene holds a Lambertian material (rtw_shade_rays)
     uint64_t scene_serial = 0;        // ++ per rtw_upload_scene
     // work buffers
     void* d_partial = nullptr;

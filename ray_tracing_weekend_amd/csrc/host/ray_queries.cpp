@@ -1,6 +1,7 @@
 // ray_queries.cpp -- hit_rays / light_pdf of the C++ host mirror (rtw_host.hpp):
 // the batched Hittable::hit and light-list pdf_value through rtw_hit_rays /
-// rtw_light_pdf_rays.  Its own unit, so that programs that link rtw_host.cpp
+// rtw_light_pdf_rays, the any-hit and light-sample queries, and the path queries
+// (camera_rays / shade_rays through rtw_camera_rays / rtw_shade_rays).  Its own unit, so that programs that link rtw_host.cpp
 // without a device (the CPU checks) need no more entry points than
 // Camera::render uses.
 #include "rtw_host.hpp"
@@ -87,6 +88,50 @@ LightSamples light_sample(const HittableList& world, const HittableList& lights,
     finish(ctx, rtw_light_sample(ctx, origins.data(), n, seed, first_stream, sample, out.directions.data(),
                                  with_pdf ? out.pdf.data() : nullptr, out.light.data()),
            "rtw_light_sample");
+    return out;
+}
+
+CameraRays camera_rays(const Camera& cam, uint64_t seed, uint32_t sample, const std::vector<uint32_t>& pixels,
+                       uint64_t first_pixel, uint64_t n, const RenderOptions& opt) {
+    if (opt.precision != RTW_F64) throw Error(RTW_E_INVALID, "the C++ mirror's ray queries are f64 (RTW_F64)");
+    if (!pixels.empty()) n = pixels.size();
+    CameraRays out;
+    out.rays.resize(6 * n);
+    out.rng.resize(4 * n);
+    RenderOptions one = opt;
+    one.device_mask = 0;
+    rtw_ctx* ctx = create_context(one);   // (camera rays need no staged scene)
+    finish(ctx, rtw_camera_rays(ctx, &cam.raw(), seed, sample, pixels.empty() ? nullptr : pixels.data(), first_pixel, n,
+                                out.rays.data(), out.rng.data()),
+           "rtw_camera_rays");
+    return out;
+}
+
+Bounces shade_rays(const HittableList& world, const HittableList& lights, const std::vector<double>& rays,
+                   const std::vector<RayHit>& hits, std::vector<uint64_t>& rng, bool with_pdfs,
+                   const RenderOptions& opt) {
+    if (rays.size() % 6) throw Error(RTW_E_INVALID, "shade_rays: rays holds 6 values per ray");
+    const size_t n = rays.size() / 6;
+    if (hits.size() != n || rng.size() != 4 * n)
+        throw Error(RTW_E_INVALID, "shade_rays: one hit record and 4 rng words per ray");
+    std::vector<double> h(9 * n);
+    std::vector<int32_t> ids(4 * n);
+    for (size_t k = 0; k < n; ++k) {
+        const RayHit& r = hits[k];
+        const double row[9] = {r.t, r.p.x, r.p.y, r.p.z, r.normal.x, r.normal.y, r.normal.z, r.u, r.v};
+        for (int q = 0; q < 9; ++q) h[9 * k + q] = row[q];
+        ids[4 * k] = r.object, ids[4 * k + 1] = r.material, ids[4 * k + 2] = r.front_face ? 1 : 0, ids[4 * k + 3] = r.kind;
+    }
+    Bounces out;
+    out.next.resize(6 * n);
+    out.weight.resize(3 * n);
+    out.emitted.resize(3 * n);
+    out.event.resize(n);
+    if (with_pdfs) out.pdfs.resize(3 * n);
+    rtw_ctx* ctx = query_context(world, lights, opt);
+    finish(ctx, rtw_shade_rays(ctx, rays.data(), h.data(), ids.data(), n, rng.data(), out.next.data(), out.weight.data(),
+                               out.emitted.data(), out.event.data(), with_pdfs ? out.pdfs.data() : nullptr),
+           "rtw_shade_rays");
     return out;
 }
 

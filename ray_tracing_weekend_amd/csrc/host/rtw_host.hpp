@@ -306,6 +306,29 @@ LightSamples light_sample(const HittableList& world, const HittableList& lights,
                           uint64_t seed, uint64_t first_stream = 0, uint32_t sample = 0, bool with_pdf = true,
                           const RenderOptions& opt = {});
 
+// Path queries (rtw_camera_rays / rtw_shade_rays, include/rtw.h), f64 on one
+// device; defined in host/ray_queries.cpp.
+// Camera::get_ray for n pixels of sample `sample`: ray k is pixel index pixels[k]
+// (j * image_width + i), or first_pixel + k with an empty list and n rays.
+struct CameraRays {
+    std::vector<double> rays;         // 6 per ray {origin, direction}
+    std::vector<uint64_t> rng;        // 4 per ray: xoshiro256++ s0..s3 after get_ray's draws
+};
+CameraRays camera_rays(const Camera& cam, uint64_t seed, uint32_t sample, const std::vector<uint32_t>& pixels = {},
+                       uint64_t first_pixel = 0, uint64_t n = 0, const RenderOptions& opt = {});
+// One iteration of ray_colour_tail_call after world.hit per ray: rays the incoming
+// rays, hits their hit_rays records; rng (4 words per ray) is advanced in place.
+struct Bounces {
+    std::vector<double> next;         // 6 per ray {p, direction}
+    std::vector<double> weight;       // 3 per ray
+    std::vector<double> emitted;      // 3 per ray
+    std::vector<int32_t> event;       // RTW_EVENT_*
+    std::vector<double> pdfs;         // 3 per ray {mixture, light list, scattering}, or empty
+};
+Bounces shade_rays(const HittableList& world, const HittableList& lights, const std::vector<double>& rays,
+                   const std::vector<RayHit>& hits, std::vector<uint64_t>& rng, bool with_pdfs = false,
+                   const RenderOptions& opt = {});
+
 // The denoiser (rtw_denoise, include/rtw.h): the filtered per-sample means
 // [H][W][3] of the colour sums [H][W][3] and the feature sums [H][W][8] of
 // render_features, for the counts [H][W] -- empty: spp for every pixel.  params
