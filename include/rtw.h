@@ -618,7 +618,13 @@ typedef struct rtw_query_stats {
                                      (rtw_light_sample: `kernel` is the light path,
                                      light_tests those of the fused pdf), 4 camera rays
                                      (rtw_camera_rays), 5 the bounce (rtw_shade_rays: `hits`
-                                     counts the rays that continue, `kernel` is the light path) */
+                                     counts the rays that continue, `kernel` is the light path),
+                                     6 one path advance (rtw_path_advance: rays = n, `hits`
+                                     counts the survivors), 7 the wavefront driver
+                                     (rtw_render_wavefront: rays = the sum of the rounds' n --
+                                     a render's `segments` --, `hits` = the SCATTER events -- its
+                                     `lambertian` --, kernel_ms = the device time of the whole
+                                     call); `kernel` is 0 for both */
     double kernel_ms;             /* device time of the query kernel (HIP events) */
 } rtw_query_stats;
 /* Counters of the last query (waits for it); RTW_E_INVALID before the first. */
@@ -796,6 +802,92 @@ int rtw_shade_rays_device(rtw_ctx *ctx, const void *d_rays, size_t rays_bytes, c
                           void *d_next, size_t next_bytes, void *d_weight, size_t weight_bytes, void *d_emitted,
                           size_t emitted_bytes, int32_t *d_event, size_t event_bytes, void *d_pdfs, size_t pdfs_bytes,
                           void *stream);
+
+/* ---- wavefront path rounds on the device: begin, advance, the batched driver ----
+ * The loop above, kept on the GPU.  A PATH STATE is five arrays of the paths
+ * still alive, row k one path: rays n x 6, rng n x 4 uint64, mult n x 3 (the
+ * product of the weights so far), res n x 3 (the emission gathered so far) and
+ * slot n uint32 -- where the path's colour goes when it ends: colour[slot], an
+ * array of colour_slots x 3 values.  The slot travels with the path; a path's
+ * result does not depend on its row.  All values are the context's precision.
+ *
+ * rtw_path_begin_device: for k < n, mult = 1, res = 0, slot = first_slot + k.
+ * first_slot + n > 2^32 is RTW_E_INVALID.  No scene needs to be staged.
+ *
+ * rtw_path_advance: one round's bookkeeping.  In: n, the state's mult / res /
+ * slot the round started from, and the round's event / weight / emitted / next /
+ * rng exactly as rtw_shade_rays wrote them for the state's rays (rng: the one
+ * it advanced in place).  Per path, each component in the context's precision,
+ * every product rounded before the add (no fused multiply-add):
+ *     MISS      colour[slot] = mult * background + res          (camera.rs:473-475)
+ *     ABSORBED  colour[slot] = mult * emitted + res             (camera.rs:484-486)
+ *     SCATTER   res' = res + mult * emitted, mult' = mult * weight, survives
+ *     REFLECT   mult' = mult * weight, res' = res, survives     (camera.rs:488-521)
+ *     any other event value ends the path as a MISS with a black background
+ * A survivor is appended to the OUT-STATE as {rays = next, rng, mult', res',
+ * slot}; with `last` set (the round at max_depth - 1) it is not appended but
+ * ends with colour[slot] = 0 + res' (camera.rs:470-472).  The number of
+ * survivors is returned: the host form writes it to *survivors, the device
+ * form to the device word *d_count, which the call itself zeroes on the stream
+ * first.  Only the survivors' rows of the out-state are written.
+ * Order: the survivors of each block of 256 consecutive input paths are
+ * contiguous in the out-state and keep their order; the order of the blocks is
+ * unspecified.  Sort by slot to compare.
+ * The step is out of place: an out-state array that shares a byte with an
+ * in-state array, a round array, colour or another out-state array is
+ * RTW_E_INVALID.  Further RTW_E_INVALID: a NULL context or array (n > 0), n or
+ * colour_slots > 2^32, in the device form a buffer smaller than n records
+ * (colour: colour_slots) or not aligned for its records (as rtw_shade_rays';
+ * mult / res / colour as weight, slot 4, d_count 8).  RTW_E_UNSUPPORTED on a
+ * multi-device or virtual-rank context.  All of these are refused before any
+ * device call.  A slot >= colour_slots: the host form refuses it
+ * (RTW_E_INVALID); in a device buffer it is the caller's error and that path's
+ * colour is skipped, not written (rtw_camera_rays_device's policy for a pixel
+ * index).  background is the camera's (3 doubles, converted to the context's
+ * precision).  No scene needs to be staged.  Query stats: is_light_pdf = 6,
+ * rays = n, hits = survivors.
+ *
+ * rtw_render_wavefront: the driver.  It adds the samples [first_sample,
+ * first_sample + n_samples) of every pixel onto sums [H x W x 3] f64 (in / out;
+ * row j = 0 is the bottom row, as rtw_render), in sample order, so windows
+ * compose bit for bit and RTW_F64 equals rtw_render at chunk 1 bit for bit.
+ * Samples run in batches of B: per batch rtw_camera_rays_device for each sample
+ * b into slots [b * W * H, (b + 1) * W * H), begin, then up to max_depth rounds
+ * of rtw_hit_rays_device (t_min = f64::EPSILON), rtw_shade_rays_device and the
+ * advance over ALL the batch's live paths, one pinned 8-byte readback of the
+ * survivor count per round (the next round's n; 0 ends the batch), and the
+ * fold sums[p][c] += (double)colour[b][p][c] for b = 0 .. B - 1 in that order.
+ * batch = 0: B = clamp(2^22 / (W * H), 1, n_samples); otherwise B = min(batch,
+ * n_samples); B x W x H > 2^32 is RTW_E_INVALID.  The state (two path states,
+ * one round's arrays, the colours: about 476 bytes a path in RTW_F64, 284 in
+ * RTW_F32) belongs to the context, grows on demand and is freed with it.
+ * max_depth = 0 adds 0 per sample.  Refused before anything is launched:
+ * what rtw_shade_rays refuses (RTW_E_NO_SCENE, RTW_E_NO_LIGHTS,
+ * RTW_E_UNSUPPORTED), a NULL cam or sums, first_sample + n_samples > 2^32, an
+ * image without pixels, in the device form d_sums smaller than H x W x 3
+ * doubles.  Query stats: is_light_pdf = 7, rays = the sum of the rounds' n (a
+ * render's `segments`), hits = the SCATTER events (its `lambertian`), kernel_ms
+ * = the device time of the whole call. */
+int rtw_path_begin_device(rtw_ctx *ctx, uint64_t n, uint32_t first_slot, void *d_mult, size_t mult_bytes, void *d_res,
+                          size_t res_bytes, uint32_t *d_slot, size_t slot_bytes, void *stream);
+int rtw_path_advance(rtw_ctx *ctx, uint64_t n, const void *mult, const void *res, const uint32_t *slot,
+                     const int32_t *event, const void *weight, const void *emitted, const void *next,
+                     const uint64_t *rng, void *out_rays, uint64_t *out_rng, void *out_mult, void *out_res,
+                     uint32_t *out_slot, void *colour, uint64_t colour_slots, const double background[3], int last,
+                     uint64_t *survivors);
+int rtw_path_advance_device(rtw_ctx *ctx, uint64_t n, const void *d_mult, size_t mult_bytes, const void *d_res,
+                            size_t res_bytes, const uint32_t *d_slot, size_t slot_bytes, const int32_t *d_event,
+                            size_t event_bytes, const void *d_weight, size_t weight_bytes, const void *d_emitted,
+                            size_t emitted_bytes, const void *d_next, size_t next_bytes, const uint64_t *d_rng,
+                            size_t rng_bytes, void *d_out_rays, size_t out_rays_bytes, uint64_t *d_out_rng,
+                            size_t out_rng_bytes, void *d_out_mult, size_t out_mult_bytes, void *d_out_res,
+                            size_t out_res_bytes, uint32_t *d_out_slot, size_t out_slot_bytes, void *d_colour,
+                            size_t colour_bytes, uint64_t colour_slots, const double background[3], int last,
+                            uint64_t *d_count, void *stream);
+int rtw_render_wavefront(rtw_ctx *ctx, const rtw_camera *cam, uint64_t seed, uint32_t first_sample,
+                         uint32_t n_samples, uint32_t batch, double *sums);
+int rtw_render_wavefront_device(rtw_ctx *ctx, const rtw_camera *cam, uint64_t seed, uint32_t first_sample,
+                                uint32_t n_samples, uint32_t batch, double *d_sums, size_t sums_bytes, void *stream);
 
 /* ---- feature buffers for denoisers: first-hit albedo, normal, distance ----
  * One fused pass over the render's own primary rays.  For pixel (i, j) and the

@@ -579,6 +579,17 @@ class Camera:
             r.set_scene(flatten(world, lights))
             return r.render_wavefront(self, seed, first_sample, n_samples, on_bounce)
 
+    def render_wavefront_batched(self, world, lights, first_sample: int = 0, n_samples: int | None = None, *,
+                                 batch: int = 0, on_bounce=None, seed: int = 0x5EED0001, precision: int = RTW_F64,
+                                 device: int = 0, accel: int = RTW_ACCEL_AUTO) -> np.ndarray:
+        """render_wavefront with its rounds on the device, `batch` samples at a
+        time (Renderer.render_wavefront_batched), with the scene staged for this
+        one call: float64 sums [H, W, 3], the same bits as render_wavefront."""
+        with Renderer(device=device, precision=precision) as r:
+            r.set_accel(accel)
+            r.set_scene(flatten(world, lights))
+            return r.render_wavefront_batched(self, seed, first_sample, n_samples, batch=batch, on_bounce=on_bounce)
+
     def render_denoised(self, world, lights, *, seed: int = 0x5EED0001, precision: int = RTW_F64, device: int = 0,
                         accel: int = RTW_ACCEL_AUTO, **params) -> np.ndarray:
         """The render, its feature pass and the denoiser on one context: the
@@ -1212,6 +1223,176 @@ class Renderer:
                 colour[paths] = 0.0 + res                                          # camera.rs:470-472
             sums = sums + f64(colour)
         return sums.reshape(H, W, 3)
+
+    # ---- wavefront path rounds on the device (rtw_path_begin_device / rtw_path_advance / rtw_render_wavefront)
+    def path_begin(self, n: int, first_slot: int = 0):
+        """The state n paths start from, as torch tensors on this device
+        (rtw_path_begin_device on torch's current stream): (mult [n, 3] of ones,
+        res [n, 3] of zeros, slot [n] int32 carrying the uint32 first_slot + k)."""
+        import torch
+        n, first_slot = int(n), int(first_slot)
+        if n < 0 or first_slot < 0 or first_slot + n > 1 << 32:
+            raise RenderError(_capi.RTW_E_INVALID, "path_begin: first_slot + n is beyond 2^32 slots")
+        dev = torch.device("cuda", self.device)
+        dt = torch.float32 if self.precision == RTW_F32 else torch.float64
+        mult = torch.empty((n, 3), dtype=dt, device=dev)
+        res = torch.empty((n, 3), dtype=dt, device=dev)
+        slot = torch.empty((n,), dtype=torch.int32, device=dev)
+        stream = _torch_stream(self.device)
+        nb = lambda t: t.numel() * t.element_size()                  # noqa: E731
+        vp = lambda t: C.c_void_p(t.data_ptr()) if n else None       # noqa: E731
+        self._check(_lib.rtw_path_begin_device(self.ctx, n, first_slot, vp(mult), nb(mult), vp(res), nb(res), vp(slot),
+                                               nb(slot), C.c_void_p(stream) if stream else None),
+                    "rtw_path_begin_device")
+        return mult, res, slot
+
+    def path_advance(self, mult, res, slot, event, weight, emitted, nxt, rng, colour, background, last: bool = False,
+                     *, out=None):
+        """One round's bookkeeping on the device (rtw_path_advance, include/rtw.h):
+        from the state (mult, res, slot) the round started with and what
+        shade_rays returned for its rays (event, weight, emitted, nxt, and the
+        rng it advanced), a path that ends writes colour[slot] (MISS: mult *
+        background + res; ABSORBED: mult * emitted + res; with `last` a survivor:
+        0 + res'), and the survivors' state (rays, rng, mult, res, slot) comes
+        back, cut to the survivor count -- the one readback of the round.  Rows:
+        the survivors of each 256 input paths stay together and in order, the
+        blocks in any order; slot names the path.  colour [slots, 3] is UPDATED
+        IN PLACE.  numpy arrays (rng uint64, slot uint32, event int32) go through
+        the host entry, which refuses a slot beyond colour; torch tensors on the
+        GPU (rng int64, slot int32, the same bits) through the device entry on
+        torch's current stream, where such a path's colour is skipped.  out: five
+        arrays / tensors of at least n rows to write the survivors into (rows
+        beyond the count are left as they are); none may overlap an input."""
+        bg = (C.c_double * 3)(*[float(v) for v in background])
+        if type(mult).__module__.split(".")[0] == "torch":
+            import torch
+            dt = torch.float32 if self.precision == RTW_F32 else torch.float64
+            n = int(mult.shape[0])
+            dev = mult.device
+            spec = (("mult", mult, dt, (n, 3)), ("res", res, dt, (n, 3)), ("slot", slot, torch.int32, (n,)),
+                    ("event", event, torch.int32, (n,)), ("weight", weight, dt, (n, 3)),
+                    ("emitted", emitted, dt, (n, 3)), ("nxt", nxt, dt, (n, 6)), ("rng", rng, torch.int64, (n, 4)))
+            for name, t, d, shape in spec:
+                if type(t).__module__.split(".")[0] != "torch" or t.dtype != d or not t.is_cuda or \
+                        t.device.index != self.device or tuple(t.shape) != shape or not t.is_contiguous():
+                    raise RenderError(_capi.RTW_E_INVALID, f"path_advance: {name} must be a contiguous {list(shape)} "
+                                                           f"{d} tensor on device {self.device}")
+            if type(colour).__module__.split(".")[0] != "torch" or colour.dtype != dt or colour.device != dev or \
+                    colour.dim() != 2 or colour.shape[1] != 3 or not colour.is_contiguous():
+                raise RenderError(_capi.RTW_E_INVALID, "path_advance: colour must be a contiguous [slots, 3] tensor of "
+                                                       "the context's precision on the state's device")
+            if out is None:
+                out = (torch.empty((n, 6), dtype=dt, device=dev), torch.empty((n, 4), dtype=torch.int64, device=dev),
+                       torch.empty((n, 3), dtype=dt, device=dev), torch.empty((n, 3), dtype=dt, device=dev),
+                       torch.empty((n,), dtype=torch.int32, device=dev))
+            o_spec = (("rays", dt, 6), ("rng", torch.int64, 4), ("mult", dt, 3), ("res", dt, 3), ("slot", torch.int32, 0))
+            for (name, d, cols), t in zip(o_spec, out):
+                if t.dtype != d or t.device != dev or not t.is_contiguous() or t.dim() != (2 if cols else 1) or \
+                        (cols and t.shape[1] != cols):
+                    raise RenderError(_capi.RTW_E_INVALID, f"path_advance: out {name} has the wrong dtype, shape or device")
+            count = torch.zeros((1,), dtype=torch.int64, device=dev)
+            stream = _torch_stream(self.device)
+            nb = lambda t: t.numel() * t.element_size()                  # noqa: E731
+            vp = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None   # noqa: E731
+            args = []
+            for t in (mult, res, slot, event, weight, emitted, nxt, rng, *out, colour):
+                args += [vp(t), nb(t)]
+            self._check(_lib.rtw_path_advance_device(self.ctx, n, *args, int(colour.shape[0]), bg, 1 if last else 0,
+                                                     C.c_void_p(count.data_ptr()),
+                                                     C.c_void_p(stream) if stream else None), "rtw_path_advance_device")
+            m = int(count.item())
+            return tuple(t[:m] for t in out)
+        dt = np.float32 if self.precision == RTW_F32 else np.float64
+        as_c = lambda a, d: np.ascontiguousarray(np.asarray(a, d))   # noqa: E731
+        mult, res, weight, emitted, nxt = (as_c(a, dt) for a in (mult, res, weight, emitted, nxt))
+        slot, event, rng = as_c(slot, np.uint32), as_c(event, np.int32), as_c(rng, np.uint64)
+        n = int(mult.shape[0])
+        for name, a, shape in (("mult", mult, (n, 3)), ("res", res, (n, 3)), ("slot", slot, (n,)), ("event", event, (n,)),
+                               ("weight", weight, (n, 3)), ("emitted", emitted, (n, 3)), ("nxt", nxt, (n, 6)),
+                               ("rng", rng, (n, 4))):
+            if a.shape != shape:
+                raise RenderError(_capi.RTW_E_INVALID, f"path_advance: {name} must be {list(shape)}")
+        if not isinstance(colour, np.ndarray) or colour.dtype != dt or colour.ndim != 2 or colour.shape[1] != 3 or \
+                not colour.flags.c_contiguous or not colour.flags.writeable:
+            raise RenderError(_capi.RTW_E_INVALID, "path_advance: colour must be a writeable C-contiguous [slots, 3] array "
+                                                   "of the context's precision (it is updated in place)")
+        if out is None:
+            out = (np.zeros((n, 6), dt), np.zeros((n, 4), np.uint64), np.zeros((n, 3), dt), np.zeros((n, 3), dt),
+                   np.zeros(n, np.uint32))
+        o_spec = (("rays", dt, (6,)), ("rng", np.uint64, (4,)), ("mult", dt, (3,)), ("res", dt, (3,)), ("slot", np.uint32, ()))
+        for (name, d, tail), a in zip(o_spec, out):
+            if not isinstance(a, np.ndarray) or a.dtype != d or a.shape[1:] != tail or a.shape[0] < n or \
+                    not a.flags.c_contiguous or not a.flags.writeable:
+                raise RenderError(_capi.RTW_E_INVALID, f"path_advance: out {name} must be a writeable C-contiguous "
+                                                       f"array of at least n rows")
+        vp = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None   # noqa: E731
+        m = C.c_uint64(0)
+        self._check(_lib.rtw_path_advance(self.ctx, n, *[vp(a) for a in (mult, res, slot, event, weight, emitted, nxt,
+                                                                         rng, *out, colour)],
+                                          int(colour.shape[0]), bg, 1 if last else 0, C.byref(m)), "rtw_path_advance")
+        return tuple(a[:m.value] for a in out)
+
+    def render_wavefront_batched(self, cam: Camera, seed: int, first_sample: int = 0, n_samples: int | None = None, *,
+                                 batch: int = 0, sums=None, on_bounce=None, as_torch: bool = False):
+        """render_wavefront with its rounds kept on the device
+        (rtw_render_wavefront): the sums [H, W, 3] float64 of the samples
+        [first_sample, first_sample + n_samples), added in sample order onto
+        `sums` -- the same bits as render_wavefront, in RTW_F64 render()'s at
+        chunk 1.  The samples run `batch` at a time through the same rounds (0:
+        as many as keep a round at 2^22 paths), so there are max_depth rounds a
+        batch, not a sample, and one 8-byte readback a round.  Without a hook
+        this is the C driver (as_torch: on torch's current stream, device sums in
+        and out).  With on_bounce the same batched loop runs here over
+        camera_rays / hit_rays / shade_rays / path_advance on torch tensors, and
+        the hook is called each round with render_wavefront's signature; paths
+        are the slots b * W * H + pixel of the live paths (b: the sample's place
+        in its batch), an int64 tensor, and the arrays are tensors on the GPU."""
+        W, H = int(cam.raw.image_width), int(cam.raw.image_height)
+        first_sample, batch = int(first_sample), int(batch)
+        n_samples = max(int(cam.raw.samples_per_pixel) - first_sample, 0) if n_samples is None else int(n_samples)
+        if batch < 0 or n_samples < 0 or first_sample < 0:
+            raise RenderError(_capi.RTW_E_INVALID, "render_wavefront_batched: a negative sample window or batch")
+        if on_bounce is None and not as_torch:
+            out = np.zeros((H, W, 3), np.float64) if sums is None else \
+                np.array(sums, np.float64).reshape(H, W, 3)
+            self._check(_lib.rtw_render_wavefront(self.ctx, C.byref(cam.raw), int(seed), first_sample, n_samples, batch,
+                                                  out.ctypes.data_as(C.POINTER(C.c_double))), "rtw_render_wavefront")
+            return out
+        import torch
+        dev = torch.device("cuda", self.device)
+        acc = torch.zeros((H, W, 3), dtype=torch.float64, device=dev) if sums is None else \
+            torch.as_tensor(sums, dtype=torch.float64, device=dev).reshape(H, W, 3).clone()
+        if on_bounce is None:
+            stream = _torch_stream(self.device)
+            self._check(_lib.rtw_render_wavefront_device(self.ctx, C.byref(cam.raw), int(seed), first_sample, n_samples,
+                                                         batch, C.c_void_p(acc.data_ptr()), acc.numel() * 8,
+                                                         C.c_void_p(stream) if stream else None),
+                        "rtw_render_wavefront_device")
+            return acc
+        px, depth_max = W * H, int(cam.raw.max_depth)
+        dt = torch.float32 if self.precision == RTW_F32 else torch.float64
+        B = min(batch if batch else max((1 << 22) // max(px, 1), 1), n_samples)
+        flat = acc.reshape(px, 3)
+        done = 0
+        while done < n_samples:
+            nb = min(B, n_samples - done)
+            pairs = [self.camera_rays(cam, seed, first_sample + done + b, as_torch=True) for b in range(nb)]
+            rays = torch.cat([p[0] for p in pairs]) if nb > 1 else pairs[0][0]
+            rng = torch.cat([p[1] for p in pairs]) if nb > 1 else pairs[0][1]
+            mult, res, slot = self.path_begin(nb * px)
+            colour = torch.zeros((nb * px, 3), dtype=dt, device=dev)
+            for depth in range(depth_max):
+                if int(rays.shape[0]) == 0:
+                    break
+                hits, ids = self.hit_rays(rays)
+                nxt, weight, emitted, event = self.shade_rays(rays, hits, ids, rng)
+                on_bounce(depth, slot.to(torch.int64) & 0xFFFFFFFF, rays, hits, ids, event, weight, emitted)
+                rays, rng, mult, res, slot = self.path_advance(mult, res, slot, event, weight, emitted, nxt, rng, colour,
+                                                               cam.background, last=depth == depth_max - 1)
+            for b in range(nb):
+                flat += colour[b * px:(b + 1) * px].to(torch.float64)
+            done += nb
+        return acc if as_torch else acc.cpu().numpy()
 
     # ---- feature buffers for denoisers (rtw_render_features)
     def render_features(self, cam: Camera, seed: int, first: int = 0, n: int | None = None, *, counts=None,

@@ -191,6 +191,16 @@ PROTOTYPES = [
                                         C.c_size_t, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                         C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                         C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("rtw_path_begin_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
+                                        C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("rtw_path_advance", C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 14 +
+                                  [C.c_uint64, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_uint64)]),
+    ("rtw_path_advance_device", C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p, C.c_size_t] * 14 +
+                                         [C.c_uint64, C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_void_p]),
+    ("rtw_render_wavefront", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32, C.c_uint32,
+                                       C.c_uint32, _f64p]),
+    ("rtw_render_wavefront_device", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32, C.c_uint32,
+                                              C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("rtw_render_features", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32, C.c_uint32,
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rtw_render_features_device", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32, C.c_uint32,

@@ -1,6 +1,6 @@
 // capi_ctx.hpp -- private to the C-ABI units (capi.cpp, capi_render.cpp,
 // capi_lpt.cpp, capi_adaptive.cpp, capi_multi.cpp, capi_query.cpp, capi_nee.cpp,
-// capi_path.cpp, capi_features.cpp, capi_denoise.cpp): the context behind include/rtw.h's rtw_ctx and the
+// capi_path.cpp, capi_wavefront.cpp, capi_features.cpp, capi_denoise.cpp): the context behind include/rtw.h's rtw_ctx and the
 // helpers they share.
 #pragma once
 
@@ -102,6 +102,17 @@ struct QueryState {
     size_t feat_counts_cap = 0;
     void* d_feat_ids = nullptr;
     size_t feat_ids_cap = 0;
+    // the wavefront path rounds (capi_wavefront.cpp): the driver's two path states, round
+    // arrays and colours in one allocation (host/wavefront_plan.hpp), the host form's sums,
+    // {the survivor count, kQueryCounters totals of a driver call} with a pinned host word
+    // for the count's readback, and the event a driver call starts at
+    void* d_wf = nullptr;
+    size_t wf_cap = 0;
+    void* d_wf_sums = nullptr;
+    size_t wf_sums_cap = 0;
+    unsigned long long* d_wf_words = nullptr;
+    unsigned long long* h_wf_count = nullptr;
+    hipEvent_t ev_span = nullptr;
     rtw_query_stats last{};
     bool any = false;                 // a query was launched
 };

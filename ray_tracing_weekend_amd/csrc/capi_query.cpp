@@ -9,6 +9,7 @@
 
 #include "capi_ctx.hpp"
 #include "host/query_plan.hpp"
+#include "wavefront_kernels.h"
 
 void destroy_query(rtw_ctx* c) {
     QueryState* q = c->query;
@@ -20,6 +21,11 @@ void destroy_query(rtw_ctx* c) {
     if (q->d_feat) (void)hipFree(q->d_feat);
     if (q->d_feat_counts) (void)hipFree(q->d_feat_counts);
     if (q->d_feat_ids) (void)hipFree(q->d_feat_ids);
+    if (q->d_wf) (void)hipFree(q->d_wf);
+    if (q->d_wf_sums) (void)hipFree(q->d_wf_sums);
+    if (q->d_wf_words) (void)hipFree(q->d_wf_words);
+    if (q->h_wf_count) (void)hipHostFree(q->h_wf_count);
+    if (q->ev_span) (void)hipEventDestroy(q->ev_span);
     if (q->ev0) (void)hipEventDestroy(q->ev0);
     if (q->ev1) (void)hipEventDestroy(q->ev1);
     delete q;
@@ -189,7 +195,9 @@ int rtw_get_query_stats(rtw_ctx* c, rtw_query_stats* out) {
     unsigned long long h[rtw::kQueryCounters] = {};
     HIP_TRY(c, hipMemcpy(h, q->d_counters, sizeof h, hipMemcpyDeviceToHost));
     float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, q->ev0, q->ev1));
+    // (a driver call spans many queries, each with its own ev0: it starts at ev_span)
+    const bool span = q->last.is_light_pdf == rtw::kQueryWavefront && q->ev_span;
+    HIP_TRY(c, hipEventElapsedTime(&ms, span ? q->ev_span : q->ev0, q->ev1));
     q->last.rays = h[rtw::kQcRays];
     q->last.hits = h[rtw::kQcHits];
     q->last.node_visits = h[rtw::kQcNodeVisits];

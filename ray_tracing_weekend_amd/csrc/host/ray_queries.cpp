@@ -1,7 +1,9 @@
 // ray_queries.cpp -- hit_rays / light_pdf of the C++ host mirror (rtw_host.hpp):
 // the batched Hittable::hit and light-list pdf_value through rtw_hit_rays /
 // rtw_light_pdf_rays, the any-hit and light-sample queries, and the path queries
-// (camera_rays / shade_rays through rtw_camera_rays / rtw_shade_rays).  Its own unit, so that programs that link rtw_host.cpp
+// (camera_rays / shade_rays through rtw_camera_rays / rtw_shade_rays) and the wavefront
+// path rounds (path_advance / render_wavefront through rtw_path_advance /
+// rtw_render_wavefront).  Its own unit, so that programs that link rtw_host.cpp
 // without a device (the CPU checks) need no more entry points than
 // Camera::render uses.
 #include "rtw_host.hpp"
@@ -133,6 +135,62 @@ Bounces shade_rays(const HittableList& world, const HittableList& lights, const 
                                out.emitted.data(), out.event.data(), with_pdfs ? out.pdfs.data() : nullptr),
            "rtw_shade_rays");
     return out;
+}
+
+PathState path_begin(const CameraRays& from, uint32_t first_slot) {
+    const size_t n = from.rays.size() / 6;
+    if ((uint64_t)first_slot + n > (uint64_t)1 << 32) throw Error(RTW_E_INVALID, "path_begin: first_slot + n is beyond 2^32 slots");
+    PathState st;
+    st.rays = from.rays;
+    st.rng = from.rng;
+    st.mult.assign(3 * n, 1.0);
+    st.res.assign(3 * n, 0.0);
+    st.slot.resize(n);
+    for (size_t k = 0; k < n; ++k) st.slot[k] = first_slot + (uint32_t)k;
+    return st;
+}
+
+PathState path_advance(const PathState& state, const Bounces& round, const std::vector<uint64_t>& rng,
+                       std::vector<double>& colour, const Colour& background, bool last, const RenderOptions& opt) {
+    if (opt.precision != RTW_F64) throw Error(RTW_E_INVALID, "the C++ mirror's ray queries are f64 (RTW_F64)");
+    const size_t n = state.slot.size();
+    if (state.mult.size() != 3 * n || state.res.size() != 3 * n || round.event.size() != n || round.weight.size() != 3 * n ||
+        round.emitted.size() != 3 * n || round.next.size() != 6 * n || rng.size() != 4 * n || colour.size() % 3)
+        throw Error(RTW_E_INVALID, "path_advance: the state's and the round's arrays hold one row per path, colour 3 per slot");
+    PathState out;
+    out.rays.resize(6 * n);
+    out.rng.resize(4 * n);
+    out.mult.resize(3 * n);
+    out.res.resize(3 * n);
+    out.slot.resize(n);
+    const double bg[3] = {background.x, background.y, background.z};
+    uint64_t m = 0;
+    RenderOptions one = opt;
+    one.device_mask = 0;
+    rtw_ctx* ctx = create_context(one);   // (an advance needs no staged scene)
+    finish(ctx, rtw_path_advance(ctx, n, state.mult.data(), state.res.data(), state.slot.data(), round.event.data(),
+                                 round.weight.data(), round.emitted.data(), round.next.data(), rng.data(), out.rays.data(),
+                                 out.rng.data(), out.mult.data(), out.res.data(), out.slot.data(), colour.data(),
+                                 colour.size() / 3, bg, last ? 1 : 0, &m),
+           "rtw_path_advance");
+    out.rays.resize(6 * m);
+    out.rng.resize(4 * m);
+    out.mult.resize(3 * m);
+    out.res.resize(3 * m);
+    out.slot.resize(m);
+    return out;
+}
+
+std::vector<double> render_wavefront(const Camera& cam, const HittableList& world, const HittableList& lights,
+                                     uint64_t seed, uint32_t first_sample, uint32_t n_samples, uint32_t batch,
+                                     std::vector<double> sums, const RenderOptions& opt) {
+    const size_t len = (size_t)cam.raw().image_width * cam.raw().image_height * 3;
+    if (sums.empty()) sums.assign(len, 0.0);
+    if (sums.size() != len) throw Error(RTW_E_INVALID, "render_wavefront: sums holds H x W x 3 values");
+    rtw_ctx* ctx = query_context(world, lights, opt);
+    finish(ctx, rtw_render_wavefront(ctx, &cam.raw(), seed, first_sample, n_samples, batch, sums.data()),
+           "rtw_render_wavefront");
+    return sums;
 }
 
 }  // namespace rtw

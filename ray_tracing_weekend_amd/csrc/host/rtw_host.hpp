@@ -329,6 +329,32 @@ Bounces shade_rays(const HittableList& world, const HittableList& lights, const 
                    const std::vector<RayHit>& hits, std::vector<uint64_t>& rng, bool with_pdfs = false,
                    const RenderOptions& opt = {});
 
+// Wavefront path rounds (rtw_path_advance / rtw_render_wavefront, include/rtw.h), f64 on
+// one device; defined in host/ray_queries.cpp.
+// The paths still alive: row k one path; slot is where its colour goes when it ends.
+struct PathState {
+    std::vector<double> rays;         // 6 per path {origin, direction}
+    std::vector<uint64_t> rng;        // 4 per path
+    std::vector<double> mult;         // 3 per path: the product of the weights so far
+    std::vector<double> res;          // 3 per path: the emission gathered so far
+    std::vector<uint32_t> slot;       // colour[3 * slot ..] is the path's
+};
+// n paths at their start: mult = 1, res = 0, slot = first_slot + k (rays and rng: camera_rays')
+PathState path_begin(const CameraRays& from, uint32_t first_slot = 0);
+// One round's bookkeeping: `state` is what the round started from, `round` what shade_rays
+// returned for state.rays, rng the words it advanced.  A path that ends writes its colour
+// (3 per slot; `colour` is updated in place); the survivors' state comes back, the
+// survivors of each 256 input paths together and in order.  last: the round at max_depth - 1.
+PathState path_advance(const PathState& state, const Bounces& round, const std::vector<uint64_t>& rng,
+                       std::vector<double>& colour, const Colour& background, bool last = false,
+                       const RenderOptions& opt = {});
+// The wavefront driver: the sums [H][W][3] of the samples [first_sample, first_sample +
+// n_samples) added onto `sums` (empty: zeros), `batch` samples a round (0: the planner's
+// choice) -- Camera::render's sums at chunk 1, bit for bit.
+std::vector<double> render_wavefront(const Camera& cam, const HittableList& world, const HittableList& lights,
+                                     uint64_t seed, uint32_t first_sample, uint32_t n_samples, uint32_t batch = 0,
+                                     std::vector<double> sums = {}, const RenderOptions& opt = {});
+
 // The denoiser (rtw_denoise, include/rtw.h): the filtered per-sample means
 // [H][W][3] of the colour sums [H][W][3] and the feature sums [H][W][8] of
 // render_features, for the counts [H][W] -- empty: spp for every pixel.  params
