@@ -271,6 +271,14 @@ int rtw_set_accel(rtw_ctx *ctx, int accel);
  * (auto group: about this many tasks; 0 = 2^17),
  * "persist" (workgroups of persistent waves that take tasks from a global counter;
  * 1 = as many as are resident at once, the default; 0 = one task per wave),
+ * "query_grid" (testing: the ray queries, the feature pass and the wavefront rounds --
+ * rtw_hit_rays, rtw_light_pdf_rays, rtw_occluded_rays, rtw_light_sample, rtw_camera_rays,
+ * rtw_shade_rays, rtw_path_begin_device, rtw_path_advance, rtw_render_wavefront and
+ * rtw_render_features, their device forms included -- launch at most this many workgroups,
+ * each walking its blocks of 256 rays (or taking its tiles) one after another; 0 = as many
+ * as are resident at once, the default; clamped to 2^20.  Every answer is the same at any
+ * value, only the order of rtw_path_advance's blocks in the out-state follows the grid; no
+ * render kernel reads it),
  * "lds" (1 = stage the sphere list in LDS when it fits, 0 = read it from HBM),
  * "robust" (f32 ray-sphere tests in closest-approach form: 1 on, 0 off,
  * 2 = by the scene's distance-to-radius ratio, the default),

@@ -97,6 +97,7 @@ int rtw_set_tuning(rtw_ctx* c, const char* key, int64_t value) {
     else if (k == "bvh_leaf") t.bvh_leaf = (uint32_t)std::min<int64_t>(value, 15);
     else if (k == "light_leaf") t.light_leaf = (uint32_t)std::min<int64_t>(value, 15);
     else if (k == "persist") t.persist = value == 1 ? rtw::kPersistResident : (uint32_t)std::min<int64_t>(value, 1 << 20);
+    else if (k == "query_grid") t.query_grid = (uint32_t)std::min<int64_t>(value, 1 << 20);
     else if (k == "light_grid") t.light_grid = (uint32_t)std::min<int64_t>(value, 1024);
     else if (k == "item_order") t.item_order = value ? 1u : 0u;
     else if (k == "hit64") t.hit64 = value ? 1u : 0u;

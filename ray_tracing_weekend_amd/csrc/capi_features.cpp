@@ -40,7 +40,7 @@ int features_device_t(rtw_ctx* c, const rtw_camera& cam, uint64_t seed, uint32_t
     p.counters = q->d_counters;
     HIP_TRY(c, hipMemsetAsync(q->d_counters, 0, (rtw::kQueryCounters + 1) * sizeof(unsigned long long), stream));
     HIP_TRY(c, hipEventRecord(q->ev0, stream));
-    const int ran = rtw::launch_primary_features(p, pl.world, pl.robust != 0, pl.hit_lds, stream);
+    const int ran = rtw::launch_primary_features(p, pl.world, pl.robust != 0, pl.hit_lds, c->knobs.query_grid, stream);
     if (ran >= 0 && ran != pl.world) return fail(c, RTW_E_DEVICE, "the launched feature kernel is not the plan's");
     if (ran < 0)
         return fail(c, RTW_E_DEVICE,

@@ -72,7 +72,7 @@ int nee_device_t(rtw_ctx* c, const NeeArgs& a, uint64_t n, hipStream_t stream) {
         p.tmin = (R)a.t_min;
         p.stack = pl.stack;
         want = pl.world;
-        ran = rtw::launch_occlusion(p, pl.world, pl.robust != 0, pl.hit_lds, stream);
+        ran = rtw::launch_occlusion(p, pl.world, pl.robust != 0, pl.hit_lds, c->knobs.query_grid, stream);
     } else {
         p.origins = reinterpret_cast<const R*>(a.in);
         p.dirs = reinterpret_cast<R*>(a.dirs);
@@ -83,7 +83,7 @@ int nee_device_t(rtw_ctx* c, const NeeArgs& a, uint64_t n, hipStream_t stream) {
         p.sample = a.sample_index;
         p.stack = pl.light_stack;
         want = pl.light_path;
-        ran = rtw::launch_light_sample(p, pl.light_path, pl.robust != 0, pl.light_lds, stream);
+        ran = rtw::launch_light_sample(p, pl.light_path, pl.robust != 0, pl.light_lds, c->knobs.query_grid, stream);
     }
     if (ran >= 0 && ran != want) return fail(c, RTW_E_DEVICE, "the launched query kernel is not the plan's");
     if (ran < 0)

@@ -87,7 +87,8 @@ int camera_device_t(rtw_ctx* c, const rtw_camera& cam, uint64_t seed, uint32_t s
     p.counters = q->d_counters;
     HIP_TRY(c, hipMemsetAsync(q->d_counters, 0, rtw::kQueryCounters * sizeof(unsigned long long), stream));
     HIP_TRY(c, hipEventRecord(q->ev0, stream));
-    return launched(c, rtw::launch_camera_rays(p, rtw::kQueryLdsMin, stream), 0, rtw::kQueryCameraRays, stream);
+    return launched(c, rtw::launch_camera_rays(p, rtw::kQueryLdsMin, c->knobs.query_grid, stream), 0, rtw::kQueryCameraRays,
+                    stream);
 }
 
 template <typename R>
@@ -112,7 +113,8 @@ int shade_device_t(rtw_ctx* c, const ShadeBufs& b, uint64_t n, hipStream_t strea
     HIP_TRY(c, hipMemsetAsync(q->d_counters, 0, rtw::kQueryCounters * sizeof(unsigned long long), stream));
     HIP_TRY(c, hipEventRecord(q->ev0, stream));
     const rtw::ShadeLaunch sl = rtw::shade_launch(pl);
-    return launched(c, rtw::launch_shade_rays(p, sl.path, sl.robust, sl.lds, stream), sl.path, rtw::kQueryShade, stream);
+    return launched(c, rtw::launch_shade_rays(p, sl.path, sl.robust, sl.lds, c->knobs.query_grid, stream), sl.path,
+                    rtw::kQueryShade, stream);
 }
 
 // the host forms' staging: one allocation of 16-byte aligned parts (the queries' record buffer)

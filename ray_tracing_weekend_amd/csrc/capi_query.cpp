@@ -82,12 +82,12 @@ int query_device_t(rtw_ctx* c, QueryKind kind, const void* d_rays, uint64_t n, d
         p.hits = reinterpret_cast<R*>(d_out);
         p.ids = d_ids;
         p.stack = pl.stack;
-        ran = rtw::launch_hit_rays(p, pl.world, pl.robust != 0, pl.hit_lds, stream);
+        ran = rtw::launch_hit_rays(p, pl.world, pl.robust != 0, pl.hit_lds, c->knobs.query_grid, stream);
         if (ran >= 0 && ran != pl.world) return fail(c, RTW_E_DEVICE, "the launched query kernel is not the plan's");
     } else {
         p.pdf = reinterpret_cast<R*>(d_out);
         p.stack = pl.light_stack;
-        ran = rtw::launch_light_pdf_rays(p, pl.light_path, pl.robust != 0, pl.light_lds, stream);
+        ran = rtw::launch_light_pdf_rays(p, pl.light_path, pl.robust != 0, pl.light_lds, c->knobs.query_grid, stream);
         if (ran >= 0 && ran != pl.light_path) return fail(c, RTW_E_DEVICE, "the launched query kernel is not the plan's");
     }
     if (ran < 0)

@@ -86,7 +86,7 @@ int advance_launch_t(rtw_ctx* c, const AdvanceBufs& b, uint64_t n, const double 
     p.count_scatter = count_scatter ? 1u : 0u;
     HIP_TRY(c, hipMemsetAsync(b.count, 0, sizeof(unsigned long long), stream));
     if (n == 0) return RTW_OK;
-    if (rtw::launch_path_advance(p, stream))
+    if (rtw::launch_path_advance(p, c->knobs.query_grid, stream))
         return fail(c, RTW_E_DEVICE, std::string("path advance launch failed: ") + hipGetErrorString(hipGetLastError()));
     return RTW_OK;
 }
@@ -176,7 +176,7 @@ int driver_run(rtw_ctx* c, const rtw_camera& cam, uint64_t seed, uint32_t first_
             using R = decltype(r);
             rtw::PathBegin<R> p{reinterpret_cast<R*>(base + at_mult[0]), reinterpret_cast<R*>(base + at_res[0]),
                                 reinterpret_cast<uint32_t*>(base + at_slot[0]), paths, 0u};
-            return rtw::launch_path_begin(p, stream);
+            return rtw::launch_path_begin(p, c->knobs.query_grid, stream);
         });
         if (rc) return fail(c, RTW_E_DEVICE, std::string("path begin launch failed: ") + hipGetErrorString(hipGetLastError()));
         // max_depth 0: every path is "alive after max_depth rounds" with res = 0 (camera.rs:470-472)
@@ -214,7 +214,7 @@ int driver_run(rtw_ctx* c, const rtw_camera& cam, uint64_t seed, uint32_t first_
             cur = nxt;
         }
         rtw::PathFold f{base + at_colour, d_sums, px * 3, B};
-        if (rtw::launch_path_fold(esz == 8, f, stream))
+        if (rtw::launch_path_fold(esz == 8, f, c->knobs.query_grid, stream))
             return fail(c, RTW_E_DEVICE, std::string("path fold launch failed: ") + hipGetErrorString(hipGetLastError()));
         done += B;
     }
@@ -255,7 +255,7 @@ int rtw_path_begin_device(rtw_ctx* c, uint64_t n, uint32_t first_slot, void* d_m
     rc = by_precision(c, [&](auto r) {
         using R = decltype(r);
         rtw::PathBegin<R> p{reinterpret_cast<R*>(d_mult), reinterpret_cast<R*>(d_res), d_slot, n, first_slot};
-        return rtw::launch_path_begin(p, s);
+        return rtw::launch_path_begin(p, c->knobs.query_grid, s);
     });
     if (rc) return fail(c, RTW_E_DEVICE, std::string("path begin launch failed: ") + hipGetErrorString(hipGetLastError()));
     return RTW_OK;

@@ -36,7 +36,9 @@ struct FParams {
 // Launches (features_f32.hip / features_f64.hip) on `stream`: p.n_tiles > 0, the
 // world / test form / LDS of the query plan (hit_kernel_exists names the kernels).
 // Each returns the world launched, or -1 (no such kernel, or the launch failed).
-int launch_primary_features(const FParams<float>& p, int world, bool robust, size_t lds_bytes, hipStream_t stream);
-int launch_primary_features(const FParams<double>& p, int world, bool robust, size_t lds_bytes, hipStream_t stream);
+int launch_primary_features(const FParams<float>& p, int world, bool robust, size_t lds_bytes, uint32_t grid_cap,
+                            hipStream_t stream);
+int launch_primary_features(const FParams<double>& p, int world, bool robust, size_t lds_bytes, uint32_t grid_cap,
+                            hipStream_t stream);
 
 }  // namespace rtw

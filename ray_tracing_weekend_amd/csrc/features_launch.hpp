@@ -13,11 +13,11 @@ namespace rtw {
 template <typename R>
 struct FeaturesEntry {
     template <int kWorld, bool kRobust>
-    static int run(const FParams<R>& p, size_t lds_bytes, hipStream_t stream) {
+    static int run(const FParams<R>& p, size_t lds_bytes, uint32_t grid_cap, hipStream_t stream) {
         if constexpr (hit_kernel_exists(sizeof(R) == 8, kWorld, kRobust)) {
             const uint64_t blocks = ((uint64_t)p.n_tiles + kQueryWaves - 1) / kQueryWaves;
-            return launch_resident(&dev::primary_features_kernel<R, kWorld, kRobust>, blocks, p, lds_bytes, stream)
-                       ? -1 : kWorld;
+            return launch_resident(&dev::primary_features_kernel<R, kWorld, kRobust>, blocks, p, lds_bytes, grid_cap,
+                                   stream) ? -1 : kWorld;
         } else {
             return -1;
         }
@@ -25,10 +25,11 @@ struct FeaturesEntry {
 };
 
 // (defined by the unit of each precision)
-#define RTW_FEATURES_UNIT(R)                                                                                          \
-    int launch_primary_features(const FParams<R>& p, int world, bool robust, size_t lds_bytes, hipStream_t stream) { \
-        return launch_table<FeaturesEntry<R>>(p, world, robust, lds_bytes, stream,                                   \
-                                              std::make_index_sequence<2 * (kWorldBvhLds + 1)>());                   \
+#define RTW_FEATURES_UNIT(R)                                                                                      \
+    int launch_primary_features(const FParams<R>& p, int world, bool robust, size_t lds_bytes, uint32_t grid_cap, \
+                                hipStream_t stream) {                                                             \
+        return launch_table<FeaturesEntry<R>>(p, world, robust, lds_bytes, grid_cap, stream,                      \
+                                              std::make_index_sequence<2 * (kWorldBvhLds + 1)>());                \
     }
 
 }  // namespace rtw

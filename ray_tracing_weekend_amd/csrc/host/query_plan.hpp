@@ -32,6 +32,18 @@ template <typename R>
 QueryPlan plan_query(const RenderKnobs& k, const DevScene<R>& sc, const SceneScale& scale,
                      const double* center = nullptr);
 
+// The grid of a query, feature or wavefront launch (query_launch.hpp launch_resident):
+// `blocks` workgroups of work, no more than `resident` fit on the GPU at once, and
+// no more than tuning "query_grid" allows (cap 0: no cap).  Never 0 for blocks > 0:
+// a workgroup walks its blocks grid-stride (or takes tiles from a counter), so one
+// workgroup does all the work of any launch.
+inline uint32_t query_grid(uint64_t blocks, uint64_t resident, uint32_t cap) {
+    uint64_t g = blocks < resident ? blocks : resident;
+    if (cap && cap < g) g = cap;
+    if (g == 0 && blocks) g = 1;
+    return (uint32_t)(g < 0xFFFFFFFFull ? g : 0xFFFFFFFFull);
+}
+
 // The kernel parameters of a feature pass planned as `q` (with the camera's
 // center): the scene, the camera as a render's kernel sees it (camera_params.hpp),
 // the samples [first, first + n) and the image's tiles.  The buffers (counts,

@@ -55,6 +55,9 @@ struct RenderKnobs {
     uint32_t persist = kPersistResident;   // workgroups of persistent waves (tasks from a
                                       // counter; default: as many as are resident at once);
                                       // 0: one task per wave
+    uint32_t query_grid = 0;          // queries, feature pass, wavefront rounds: at most this many
+                                      // workgroups a launch (query_plan.hpp query_grid); 0: as many
+                                      // as are resident at once
     uint32_t light_leaf = 0;          // light spheres per light-BVH leaf; 0 = 4
     uint32_t light_grid = 8;          // light pdf through the light grid at light_grid / 16
                                       // cells per light (set before rtw_set_scene); 0: light BVH

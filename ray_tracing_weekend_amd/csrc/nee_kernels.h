@@ -44,9 +44,13 @@ constexpr bool light_sample_kernel_exists(bool f64, int path, bool robust) {
 // world / light path launched, or -1 (no such kernel, or the launch failed).
 // lds_bytes: QueryPlan::hit_lds / light_lds -- the any-hit stages what the
 // closest-hit query stages; it leaves the stealing area unused.
-int launch_occlusion(const NParams<float>& p, int world, bool robust, size_t lds_bytes, hipStream_t stream);
-int launch_occlusion(const NParams<double>& p, int world, bool robust, size_t lds_bytes, hipStream_t stream);
-int launch_light_sample(const NParams<float>& p, int path, bool robust, size_t lds_bytes, hipStream_t stream);
-int launch_light_sample(const NParams<double>& p, int path, bool robust, size_t lds_bytes, hipStream_t stream);
+int launch_occlusion(const NParams<float>& p, int world, bool robust, size_t lds_bytes, uint32_t grid_cap,
+                     hipStream_t stream);
+int launch_occlusion(const NParams<double>& p, int world, bool robust, size_t lds_bytes, uint32_t grid_cap,
+                     hipStream_t stream);
+int launch_light_sample(const NParams<float>& p, int path, bool robust, size_t lds_bytes, uint32_t grid_cap,
+                        hipStream_t stream);
+int launch_light_sample(const NParams<double>& p, int path, bool robust, size_t lds_bytes, uint32_t grid_cap,
+                        hipStream_t stream);
 
 }  // namespace rtw

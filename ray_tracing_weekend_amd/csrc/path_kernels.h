@@ -65,9 +65,13 @@ constexpr uint32_t record_align(size_t bytes) { return bytes % 16 == 0 ? 16u : b
 // Launches (path_f32.hip / path_f64.hip) on `stream`: p.n > 0.  launch_shade_rays
 // returns the light path launched, launch_camera_rays 0; -1: no such kernel, or
 // the launch failed.  lds_bytes: kQueryLdsMin / QueryPlan::light_lds.
-int launch_camera_rays(const CParams<float>& p, size_t lds_bytes, hipStream_t stream);
-int launch_camera_rays(const CParams<double>& p, size_t lds_bytes, hipStream_t stream);
-int launch_shade_rays(const SParams<float>& p, int path, bool robust, size_t lds_bytes, hipStream_t stream);
-int launch_shade_rays(const SParams<double>& p, int path, bool robust, size_t lds_bytes, hipStream_t stream);
+int launch_camera_rays(const CParams<float>& p, size_t lds_bytes, uint32_t grid_cap,
+                       hipStream_t stream);
+int launch_camera_rays(const CParams<double>& p, size_t lds_bytes, uint32_t grid_cap,
+                       hipStream_t stream);
+int launch_shade_rays(const SParams<float>& p, int path, bool robust, size_t lds_bytes, uint32_t grid_cap,
+                      hipStream_t stream);
+int launch_shade_rays(const SParams<double>& p, int path, bool robust, size_t lds_bytes, uint32_t grid_cap,
+                      hipStream_t stream);
 
 }  // namespace rtw

@@ -68,9 +68,15 @@ constexpr bool light_kernel_exists(bool f64, int path, bool robust) {
 
 // Launches (query_f32.hip / query_f64.hip) on `stream`: p.n > 0.  Each returns
 // the world / light path launched, or -1 (no such kernel, or the launch failed).
-int launch_hit_rays(const QParams<float>& p, int world, bool robust, size_t lds_bytes, hipStream_t stream);
-int launch_hit_rays(const QParams<double>& p, int world, bool robust, size_t lds_bytes, hipStream_t stream);
-int launch_light_pdf_rays(const QParams<float>& p, int path, bool robust, size_t lds_bytes, hipStream_t stream);
-int launch_light_pdf_rays(const QParams<double>& p, int path, bool robust, size_t lds_bytes, hipStream_t stream);
+// grid_cap: tuning "query_grid" -- at most that many workgroups (0: the resident grid),
+// for these and every other launch of query_launch.hpp's launch_resident.
+int launch_hit_rays(const QParams<float>& p, int world, bool robust, size_t lds_bytes, uint32_t grid_cap,
+                    hipStream_t stream);
+int launch_hit_rays(const QParams<double>& p, int world, bool robust, size_t lds_bytes, uint32_t grid_cap,
+                    hipStream_t stream);
+int launch_light_pdf_rays(const QParams<float>& p, int path, bool robust, size_t lds_bytes, uint32_t grid_cap,
+                          hipStream_t stream);
+int launch_light_pdf_rays(const QParams<double>& p, int path, bool robust, size_t lds_bytes, uint32_t grid_cap,
+                          hipStream_t stream);
 
 }  // namespace rtw

@@ -61,10 +61,11 @@ struct PathFold {
 };
 
 // Launches (wavefront.hip) on `stream`: n > 0.  0, or -1: the launch failed.
-int launch_path_begin(const PathBegin<float>& p, hipStream_t stream);
-int launch_path_begin(const PathBegin<double>& p, hipStream_t stream);
-int launch_path_advance(const PathAdvance<float>& p, hipStream_t stream);
-int launch_path_advance(const PathAdvance<double>& p, hipStream_t stream);
-int launch_path_fold(bool f64, const PathFold& p, hipStream_t stream);
+// grid_cap: tuning "query_grid" (query_kernels.h).
+int launch_path_begin(const PathBegin<float>& p, uint32_t grid_cap, hipStream_t stream);
+int launch_path_begin(const PathBegin<double>& p, uint32_t grid_cap, hipStream_t stream);
+int launch_path_advance(const PathAdvance<float>& p, uint32_t grid_cap, hipStream_t stream);
+int launch_path_advance(const PathAdvance<double>& p, uint32_t grid_cap, hipStream_t stream);
+int launch_path_fold(bool f64, const PathFold& p, uint32_t grid_cap, hipStream_t stream);
 
 }  // namespace rtw

@@ -49,6 +49,43 @@ def test_query_plan_known_answers_and_sweep():
     assert r.stdout.rstrip().endswith("\n0 wrong")
 
 
+@functools.lru_cache(maxsize=None)
+def query_grid_check_exe(sanitize=False):
+    """tests/native/query_grid_check.cpp over the header's grid function, compiled once per test run."""
+    out = tempfile.mkdtemp(prefix="query_grid_check_")
+    atexit.register(shutil.rmtree, out, ignore_errors=True)
+    exe = os.path.join(out, "query_grid_check")
+    flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] if sanitize else ["-O2"]
+    subprocess.run([HIPCC, "-x", "hip", "--cuda-host-only", *flags, "-std=c++17", "-ffp-contract=off", "-I", CSRC,
+                    "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "native", "query_grid_check.cpp"),
+                    "-o", exe], check=True, capture_output=True, timeout=300)
+    return exe
+
+
+@needs_hipcc
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "sanitizers"])
+def test_query_grid_is_the_smallest_of_blocks_resident_and_cap(sanitize):
+    """Tuning "query_grid": cap 0 (off) at blocks above, equal to and below the
+    resident count, cap 1, cap > blocks, a huge cap, never 0 for blocks > 0; the
+    same stand-alone host program also under the address and undefined-behaviour
+    sanitizers."""
+    r = subprocess.run([query_grid_check_exe(sanitize)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert r.stdout.rstrip().endswith("\n0 wrong")
+    assert "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+
+
+def test_query_grid_key_is_in_the_header_key_list():
+    """The key is documented next to "persist" in rtw.h's key list, and a NULL
+    context refuses it before any HIP call.  (A context needs a device:
+    tests/test_gpu_query_grid.py sets the key, sees -1 refused and the value
+    clamped and sets it on a virtual-rank context.)"""
+    header = open(os.path.join(ROOT, "include", "rtw.h")).read()
+    keys = header[header.index("scheduling knobs"):header.index("int rtw_set_tuning")]
+    assert '"query_grid"' in keys and '"persist"' in keys
+    assert rtw._lib.rtw_set_tuning(None, b"query_grid", 1) == _capi.RTW_E_INVALID
+
+
 def _symbol(kind, prec, a, robust):
     name = {"hit": "15hit_rays_kernel", "light": "21light_pdf_rays_kernel"}[kind]
     return f"_ZN3rtw3dev{name}I{'f' if prec == 'f32' else 'd'}Li{a}ELb{robust}EEEvNS_7QParamsIT_EE"
