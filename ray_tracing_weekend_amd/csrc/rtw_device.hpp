@@ -703,9 +703,14 @@ __device__ __forceinline__ void sphere_uv(V3<double> n, double& u, double& v) {
     u = ::atan2(-n.z, n.x) / P<double>::kTau;
     v = ::acos(n.y) / P<double>::kPi;
 }
+// f32: (p - c) * rcp(r) at the pole of a large sphere can land an ulp outside
+// [-1, 1] (the ground sphere of the Book-1 scenes: r = 1000), where acosf is
+// NaN; the argument is clamped (by compares, so that a NaN n.y stays NaN).
+// The f64 overload above is the reference's bit for bit and is not clamped.
 __device__ __forceinline__ void sphere_uv(V3<float> n, float& u, float& v) {
     u = ::atan2f(-n.z, n.x) * 0.159154943091895335769f;
-    v = ::acosf(n.y) * P<float>::kInvPi;
+    const float y = n.y > 1.f ? 1.f : (n.y < -1.f ? -1.f : n.y);
+    v = ::acosf(y) * P<float>::kInvPi;
 }
 
 }  // namespace dev

@@ -112,6 +112,9 @@ def test_refusals(r64):
 
 
 def test_f32_rays_follow_the_f64_ones_and_draw_the_same_words():
+    """(The absolute bound below is the coarse one; tests/test_gpu_f32_records.py
+    test_camera_rays holds the f32 rays, with and without defocus, to the law of the f32
+    form within 4 x the rounding of a correctly rounded f32 evaluation.)"""
     cam, camd = cams("simple")
     want_rays, want_rng = P.camera_rays(camd, SEED, range(W * H), 1)
     with rtw.Renderer(device=0, precision=rtw.RTW_F32) as r:

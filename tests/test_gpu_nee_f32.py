@@ -7,8 +7,10 @@ Against the f64 truth at t / 2 and 2 t the share of differing rays is held to
 the 1 % cap of test_f32_query_against_f64_on_camera_rays.
 
 Light sample: the list index is an integer draw and equals f64's exactly; the
-fused pdf is the f32 light pdf of {origin, direction} bit for bit; no bound on
-the directions is asserted, as for the f32 light pdf."""
+fused pdf is the f32 light pdf of {origin, direction} bit for bit.  The values
+-- t and the whole hit record behind the occlusion identity, the directions and
+the pdf -- are held row by row to the law of the f32 forms in
+tests/test_gpu_f32_records.py (test_hit_records, test_light_sample)."""
 import numpy as np
 import pytest
 

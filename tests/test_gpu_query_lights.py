@@ -127,7 +127,8 @@ def test_f32_query_against_f64_on_camera_rays():
     # numpy input of another dtype is converted: the f64 rays through the f32 context
     h, i, _ = query(soa, rays, precision=rtw.RTW_F32)
     assert np.array_equal(i, i32) and same(h, h32)
-    # the light pdf in f32 runs (its values are the speed mode's: no bound is asserted)
+    # the light pdf in f32 runs; its values are held row by row to the law of the f32 form in
+    # tests/test_gpu_f32_records.py (test_light_pdf)
     b = Q.lambertian_bounces(Q.segments("simple"))
     p32, st = light_pdf(soa, b, precision=rtw.RTW_F32)
     assert p32.dtype == np.float32 and p32.shape == (len(b),) and st.kernel == LINEAR

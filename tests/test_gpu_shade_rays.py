@@ -288,7 +288,10 @@ def test_refusals():
 def test_f32_events_without_a_draw_and_the_light_pdf():
     """f32: the events that involve no draw are exact from the material kind of
     ids; the answers are deterministic from call to call; the light list's pdf of a
-    SCATTER row is light_pdf of {p, direction} of the same context bit for bit."""
+    SCATTER row is light_pdf of {p, direction} of the same context bit for bit.
+    The values of every branch (directions, weights, pdfs, texture colours, the state
+    after the draws) are held to the law of the f32 forms in
+    tests/test_gpu_f32_records.py (test_shade_rays)."""
     for name in ("simple", "cornell_box", "lights64"):
         b = P.bounces(name)
         rays = b.rays[~np.isnan(b.rays).any(1)].astype(np.float32)
