@@ -4,13 +4,15 @@
 // against a brute-force sweep (every hit light counted exactly once), whole
 // and cut into pieces as the wave-cooperative walk cuts it.  The f32 instance
 // that the f64 kernels' cooperative walk runs on the grid rounded to f32
-// (lights_pdf_grid_coop64) has no such check of its own: it is only RUN on the
-// GPU by tests/test_gpu_f64_culls.py (scenes whose light queries start 10^4
-// away, or 2^22 from the origin, at 1/16 to 16 cells per light, every pixel
-// the oracle's), and tests/test_gpu_cull_probe.py checks its candidate test
-// (light_may_hit) record by record.  Those renders do not notice a wrong
-// padding bound: with the host's pad term 1e-3 cell set to 0 they all still
-// pass.  A check of the f32 walk against a brute-force sweep is still missing.
+// (lights_pdf_grid_coop64), and the f32 kernels' own, get the same sweep on the
+// GPU: tests/native/coop_probe.hip (tests/test_gpu_coop_probe.py) walks the
+// pieces of every cut 1, 2, 3, 7 and `cells` over grids staged by
+// host/stage_scene.cpp -- the layer at 1/16 to 16 cells per light, 10^4 from
+// the origin, at 2^+-10, and with spheres that end on a cell plane and rays
+// that graze them there -- and counts each light the reference gives a pdf
+// (the kernels' light_hit_f32 hits) exactly once; with the host's pad terms set
+// to 0 that test fails, which the renders of tests/test_gpu_f64_culls.py
+// (every pixel the oracle's, at the same densities and offsets) do not notice.
 #pragma once
 
 #include <math.h>
