@@ -1284,7 +1284,8 @@ __global__ void __launch_bounds__((64 * kernel_waves<R, kWorld, kOpt>()), (kerne
                         }
                         if constexpr (kHit64) {
                             // the Lambertian direction in f64 from the f64 normal (same
-                            // words, the f64 kernels' arithmetic; with the azimuth's sin /
+                            // words, the f64 kernels' forms -- FMA-contracted in this unit, DESIGN.md
+                            // §2b: within rounding of them, not their bits; with the azimuth's sin /
                             // cos in f32 it was 1.9 % faster, but the paths' statistics fell
                             // back to the f32 direction's: profiles/r05_hit64_trig32_ab.jsonl)
                             V3<double> nl = to64(nrm);
@@ -1382,6 +1383,7 @@ __global__ void __launch_bounds__((64 * kernel_waves<R, kWorld, kOpt>()), (kerne
                 }
             }
             if (done) {
+                RTW_PROBE_SAMPLE_END();
                 // the item's running sum lives in its chunk-sum slot, not in
                 // registers: (0 + s_first) on the first sample, then slot + s
                 // -- the fold of camera.rs:323-335 in the same order

@@ -39,10 +39,12 @@
 // object id]; g_nan[0]: NaN at any other point of the path, counted at the
 // sample's end).
 //
-// RTW_TRACE (tools/trace_paths.py): record every segment of the first
-// kTraceSamples samples of one pixel -- the ray (origin, direction) and the
-// closest hit (object id, t) -- into a device array the tool reads back with
-// rtw_probe_trace_read_f32 / _f64 (exported by the trace build only).
+// RTW_TRACE (tools/trace_paths.py, tests/test_gpu_hit64_replay.py): record every
+// segment of the first kTraceSamples samples of up to kTracePix pixels -- the ray
+// (origin, direction; hit64: the f64 ray), the closest hit (object id, t, the f32
+// traversal's t) and the sphere the ray starts on -- and every such sample's colour
+// into device arrays read back with rtw_probe_trace_read_f32 / _f64 and
+// rtw_probe_trace_read_col_f32 / _f64 (exported by the trace build only).
 #pragma once
 
 #define RTW_CAT2(a, b) a##b
@@ -253,37 +255,78 @@ extern "C" int rtw_probe_timeline_read(unsigned long long* out, size_t n, int re
 
 #ifdef RTW_TRACE
 // build with -DRTW_TRACE=f32 (render_f32.hip) / -DRTW_TRACE=f64 (render_f64.hip):
-// each instantiation unit keeps its own trace array and exports its reader
+// each instantiation unit keeps its own trace arrays and exports its readers
 // (this header is included inside namespace rtw::dev)
-constexpr uint32_t kTraceSamples = 64, kTraceSegs = 64, kTraceRec = 8;
-static __device__ double g_trace[kTraceSamples * kTraceSegs * kTraceRec];
-static __device__ unsigned long long g_trace_pix = ~0ull;
-// set the traced pixel (j * W + i) and clear the array / copy it out (n doubles)
-extern "C" int RTW_CAT(rtw_probe_trace_set_, RTW_TRACE)(unsigned long long pix) {
-    static double zero[kTraceSamples * kTraceSegs * kTraceRec];
-    for (auto& z : zero) z = -2.0;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_trace), zero, sizeof zero) != hipSuccess) return -1;
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_trace_pix), &pix, sizeof pix) == hipSuccess ? 0 : -1;
+constexpr uint32_t kTracePix = 64, kTraceSamples = 64, kTraceSegs = 64, kTraceRec = 12, kTraceCol = 4;
+constexpr size_t kTraceN = (size_t)kTracePix * kTraceSamples * kTraceSegs * kTraceRec;
+constexpr size_t kTraceColN = (size_t)kTracePix * kTraceSamples * kTraceCol;
+static __device__ double g_trace[kTraceN];
+static __device__ double g_trace_col[kTraceColN];
+static __device__ unsigned long long g_trace_pix[kTracePix];
+// the traced pixels (j * W + i each, at most kTracePix; slot k of the arrays is
+// pixels[k]): set them and clear both arrays to -2
+extern "C" int RTW_CAT(rtw_probe_trace_set_list_, RTW_TRACE)(const unsigned long long* pixels, size_t n) {
+    static double blank[kTraceN];
+    static unsigned long long pix[kTracePix];
+    if (n > kTracePix) return -1;
+    for (auto& z : blank) z = -2.0;
+    for (size_t k = 0; k < kTracePix; ++k) pix[k] = k < n ? pixels[k] : ~0ull;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_trace), blank, sizeof blank) != hipSuccess) return -1;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_trace_col), blank, kTraceColN * sizeof(double)) != hipSuccess) return -1;
+    return hipMemcpyToSymbol(HIP_SYMBOL(g_trace_pix), pix, sizeof pix) == hipSuccess ? 0 : -1;
 }
+// one traced pixel (slot 0)
+extern "C" int RTW_CAT(rtw_probe_trace_set_, RTW_TRACE)(unsigned long long pix) {
+    return RTW_CAT(rtw_probe_trace_set_list_, RTW_TRACE)(&pix, 1);
+}
+// copy out the first n doubles of the segment records / of the samples' colours
 extern "C" int RTW_CAT(rtw_probe_trace_read_, RTW_TRACE)(double* out, size_t n) {
-    n = n < (size_t)kTraceSamples * kTraceSegs * kTraceRec
-            ? n : (size_t)kTraceSamples * kTraceSegs * kTraceRec;
+    n = n < kTraceN ? n : kTraceN;
     if (hipDeviceSynchronize() != hipSuccess) return -1;
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_trace), n * sizeof(double)) == hipSuccess ? (int)n : -1;
 }
-// {object id (-1 miss), t, origin xyz, direction xyz} of segment max_depth - depth
+extern "C" int RTW_CAT(rtw_probe_trace_read_col_, RTW_TRACE)(double* out, size_t n) {
+    n = n < kTraceColN ? n : kTraceColN;
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_trace_col), n * sizeof(double)) == hipSuccess ? (int)n : -1;
+}
+__device__ __forceinline__ int trace_slot(unsigned long long pix) {
+    for (uint32_t k = 0; k < kTracePix; ++k)
+        if (g_trace_pix[k] == pix) return (int)k;
+    return -1;
+}
+// segment max_depth - depth of sample s of a traced pixel: {object id (-1 miss), t
+// (hit64: the f64 t), origin xyz, direction xyz (hit64: o64 and d64, else the
+// kernel's o and d widened), the f32 traversal's t, the sphere the ray starts on
+// (-1 none), whether that sphere is isolated, depth}
 #define RTW_PROBE_SEGMENT() \
     do { \
-        if (pix_now() == g_trace_pix && s < kTraceSamples && p.max_depth - depth < kTraceSegs) { \
-            double* rec = g_trace + ((size_t)s * kTraceSegs + (p.max_depth - depth)) * kTraceRec; \
+        const int slot_ = s < kTraceSamples && p.max_depth - depth < kTraceSegs ? trace_slot(pix_now()) : -1; \
+        if (slot_ >= 0) { \
+            double* rec = g_trace + \
+                          (((size_t)slot_ * kTraceSamples + s) * kTraceSegs + (p.max_depth - depth)) * kTraceRec; \
             double t64 = (double)tb, ox = (double)o.x, oy = (double)o.y, oz = (double)o.z; \
-            if constexpr (kHit64) { t64 = tb64; ox = o64.x; oy = o64.y; oz = o64.z; } \
+            double dx = (double)d.x, dy = (double)d.y, dz = (double)d.z; \
+            if constexpr (kHit64) { \
+                t64 = tb64; ox = o64.x; oy = o64.y; oz = o64.z; dx = d64.x; dy = d64.y; dz = d64.z; \
+            } \
             rec[0] = (double)best; rec[1] = t64; rec[2] = ox; rec[3] = oy; rec[4] = oz; \
-            rec[5] = (double)d.x; rec[6] = (double)d.y; rec[7] = (double)d.z; \
+            rec[5] = dx; rec[6] = dy; rec[7] = dz; rec[8] = (double)tb; rec[9] = (double)self_s; \
+            rec[10] = self_iso ? 1.0 : 0.0; rec[11] = (double)depth; \
+        } \
+    } while (0)
+// the end of sample s of a traced pixel: {col rgb, depth left}
+#define RTW_PROBE_SAMPLE_END() \
+    do { \
+        const int slot_ = s < kTraceSamples ? trace_slot(pix_now()) : -1; \
+        if (slot_ >= 0) { \
+            double* rec = g_trace_col + ((size_t)slot_ * kTraceSamples + s) * kTraceCol; \
+            rec[0] = (double)col.x; rec[1] = (double)col.y; rec[2] = (double)col.z; rec[3] = (double)depth; \
         } \
     } while (0)
 #else
 #define RTW_PROBE_SEGMENT()
+#define RTW_PROBE_SAMPLE_END()
 #endif
 
 #ifdef RTW_PROF

@@ -5,8 +5,11 @@
     python tools/trace_paths.py build                 # here (hipcc cross-compiles)
     python tools/trace_paths.py run --out X.npz [--pixels i,j;i,j...] [--tuning hit64=1]
 
-Each traced pixel's first 64 samples record, per segment, the ray (origin,
-direction) and the closest hit (object id, t) -- rtw_probes.hpp RTW_TRACE.
+Each traced pixel's first 64 samples record, per segment, 12 doubles: the closest
+hit (object id, t), the ray (origin, direction; hit64: the f64 ray), the f32
+traversal's t, the sphere the ray starts on, whether it is isolated, and the
+depth left -- rtw_probes.hpp RTW_TRACE (the first 8 are the record this tool
+has always read; tests/test_gpu_hit64_replay.py traces 64 pixels a render).
 Both precisions draw the same RNG words, so a path is the same in both until
 a decision flips; the npz holds the records of f64 and f32 for every pixel.
 """
@@ -51,7 +54,8 @@ def run(a):
     pixels = [tuple(int(v) for v in p.split(",")) for p in a.pixels.split(";")]
     tuning = [(k, int(v)) for k, v in (kv.split("=") for kv in filter(None, a.tuning.split(",")))]
     out = {}
-    n = 64 * 64 * 8
+    rec = 12                                     # rtw_probes.hpp kTraceRec
+    n = 64 * 64 * rec                            # the first traced pixel's records
     buf = (C.c_double * n)()
     for prec, tag in ((rtw.RTW_F64, "f64"), (rtw.RTW_F32, "f32")):
         setf = getattr(lib, f"rtw_probe_trace_set_{tag}")
@@ -69,7 +73,7 @@ def run(a):
                 assert setf(j * W + i) == 0
                 r.render(cam, 5)
                 assert readf(buf, n) == n
-                recs.append(np.frombuffer(buf, np.float64).reshape(64, 64, 8).copy())
+                recs.append(np.frombuffer(buf, np.float64).reshape(64, 64, rec).copy())
         out[tag] = np.stack(recs)
     np.savez_compressed(a.out, pixels=np.array(pixels), **out)
     f64, f32 = out["f64"], out["f32"]
