@@ -632,7 +632,10 @@ typedef struct rtw_query_stats {
                                      (rtw_render_wavefront: rays = the sum of the rounds' n --
                                      a render's `segments` --, `hits` = the SCATTER events -- its
                                      `lambertian` --, kernel_ms = the device time of the whole
-                                     call); `kernel` is 0 for both */
+                                     call); `kernel` is 0 for both; 8 direct lighting
+                                     (rtw_direct_light: rays = the (point, sample) pairs traced,
+                                     `hits` = the pairs that added a term, light_tests those
+                                     of the fused pdf, `kernel` is the world) */
     double kernel_ms;             /* device time of the query kernel (HIP events) */
 } rtw_query_stats;
 /* Counters of the last query (waits for it); RTW_E_INVALID before the first. */
@@ -700,6 +703,73 @@ int rtw_light_sample(rtw_ctx *ctx, const void *origins, uint64_t n, uint64_t see
 int rtw_light_sample_device(rtw_ctx *ctx, const void *d_origins, uint64_t n, uint64_t seed, uint64_t first_stream,
                             uint32_t sample, void *d_directions, size_t directions_bytes, void *d_pdf,
                             size_t pdf_bytes, int32_t *d_light, size_t light_bytes, void *stream);
+
+/* ---- direct lighting as one query ------------------------------------------
+ * rtw_direct_light: for n shading points {p, normal} and S = n_samples light
+ * samples each, the light half of the reference's Lambertian bounce followed by
+ * the next segment's emission (camera.rs:480-521), folded per point.  It fuses
+ * what the queries above answer one by one -- rtw_light_sample, rtw_hit_rays,
+ * the `emitted` of rtw_shade_rays -- through the same device functions, on the
+ * same plan (world, test form, stacks, LDS, light path), so every field below
+ * is those queries' bit for bit in each precision.
+ *
+ * The estimator is the light list's lobe alone: direction and pdf are
+ * lights.random / lights.pdf_value, not the reference's MixturePdf with the
+ * cosine lobe.  An emitter that is not in the light list counts only where a
+ * listed light's direction passes it.  The caller multiplies the sums by the
+ * surface's albedo (the feature pass's) and divides by the samples taken.
+ *
+ * The law, per point k, over s = first_sample .. first_sample + S - 1 in that
+ * order:
+ *   1. the stream Rng(seed, first_stream + k, s) -- rtw_light_sample's keying,
+ *      with `sample` = s; from its start, d and the list index are exactly
+ *      rtw_light_sample's (hittable_list.rs:414-419);
+ *   2. pdf = lights.pdf_value(p, d): rtw_light_pdf_rays of {p, d} bit for bit,
+ *      through whichever light path the plan picks (linear, light BVH, grid,
+ *      mixed; the RTW_LIGHTS_BVH_LEAF form included);
+ *   3. the closest hit of {p, d} over t_min..=inf: rtw_hit_rays' record (t, object
+ *      id, material id, u, v, the hit point);
+ *   4. Le = Material::emitted(u, v, hit point) of that material: rtw_shade_rays'
+ *      `emitted` -- DiffuseLight's texture, black for every other material and
+ *      for a miss;
+ *   5. spdf = max(dot(normal, normalize(d)) / PI, 0) (material.rs:372-375);
+ *   6. a term is added only when there is a hit, pdf > 0 and spdf > 0 (the
+ *      comparisons are false for NaN);
+ *   7. term_c = (Le_c * spdf) / pdf, in the context's precision;
+ *   8. direct[k][c] += (double)term_c: one f64 add, never contracted;
+ *   9. when no term is added, no add is made and the record's term is 0.
+ * A point whose normal is exactly (0, 0, 0) -- a miss row of rtw_hit_rays -- is
+ * skipped entirely: no draws, no traversal, its sums untouched, its records 0
+ * with object id -1.
+ *   points    : n x 6 {p xyz, normal xyz} in the context's precision: fields 1..6
+ *               of a rtw_hit_rays record
+ *   direct    : n x 3 f64 sums in both precisions (as the feature pass folds);
+ *               overwritten, or continued from its content when accumulate != 0,
+ *               so windows over first_sample compose bit for bit
+ *   samples   : optional (NULL), n * S x 12 in the context's precision, row
+ *               k * S + (s - first_sample): {d xyz, pdf, t (0 for a miss), spdf,
+ *               Le rgb, term rgb}
+ *   sample_ids: optional (NULL), n * S x 4 int32: {light-list index drawn, object
+ *               id hit or -1, material id, 1 if the sample added a term}
+ * Calls compose over first_stream as rtw_light_sample's do.  Device form: each
+ * d_ pointer is followed by its size in bytes; d_points must be 16-byte aligned
+ * in f64 and 8-byte in f32, d_direct 8-byte, d_samples and d_sample_ids 16-byte.
+ * Errors: RTW_E_INVALID for a NULL context, NULL points or direct with n > 0,
+ * short or misaligned device buffers, a t_min that is not finite and >= 0,
+ * n_samples == 0, an empty light list (the reference panics, hittable_list.rs:
+ * 417), or n * S over 2^32 when records are asked for; RTW_E_NO_SCENE before
+ * rtw_set_scene; RTW_E_UNSUPPORTED on multi-device and virtual contexts.  n = 0
+ * launches nothing.  Query stats: is_light_pdf = 8, rays = the (point, sample)
+ * pairs traced, hits = the pairs that added a term, light_tests those of the
+ * fused pdf, kernel = the world that ran, node_visits and sphere_tests as in
+ * the closest hit. */
+int rtw_direct_light(rtw_ctx *ctx, const void *points, uint64_t n, uint64_t seed, uint64_t first_stream,
+                     uint32_t first_sample, uint32_t n_samples, double t_min, int accumulate, double *direct,
+                     void *samples, int32_t *sample_ids);
+int rtw_direct_light_device(rtw_ctx *ctx, const void *d_points, size_t points_bytes, uint64_t n, uint64_t seed,
+                            uint64_t first_stream, uint32_t first_sample, uint32_t n_samples, double t_min,
+                            int accumulate, double *d_direct, size_t direct_bytes, void *d_samples,
+                            size_t samples_bytes, int32_t *d_sample_ids, size_t sample_ids_bytes, void *stream);
 
 /* ---- path queries: camera rays and the material bounce ---------------------
  * The Material trait (shared/src/material.rs:32-49) and Camera::get_ray as

@@ -248,6 +248,18 @@ class HittableList:                          # hittable_collections/hittable_lis
             r.set_scene(flatten(world if world is not None else HittableList(), self))
             return r.light_sample(origins, seed, first_stream, sample, pdf)
 
+    def direct_light(self, points, seed: int, n_samples: int = 1, first_stream: int = 0, first_sample: int = 0,
+                     t_min: float | None = None, *, lights, records: bool = False, precision: int = RTW_F64,
+                     device: int = 0, accel: int = RTW_ACCEL_AUTO):
+        """Direct lighting of n points [n, 6] {p, normal} in this list as the
+        world, from the light list `lights`: the sums [n, 3] (and the sample
+        records) as Renderer.direct_light gives them.  Stages the scene for
+        this one call; keep a Renderer for repeated queries."""
+        with Renderer(device=device, precision=precision) as r:
+            r.set_accel(accel)
+            r.set_scene(flatten(self, lights))
+            return r.direct_light(points, seed, n_samples, first_stream, first_sample, t_min, records=records)
+
 
 class BoundedVolumeHierarchy(HittableList):  # hittable_collections/bvh.rs:106-143 (::from(list))
     """The reference's BVH over a list: as the world it gives the list's
@@ -1023,6 +1035,114 @@ class Renderer:
                                           p.ctypes.data_as(C.c_void_p) if pdf and n else None,
                                           light.ctypes.data_as(C.c_void_p)), "rtw_light_sample")
         return dirs, p, light
+
+    # ---- direct lighting as one query (rtw_direct_light)
+    def direct_light(self, points, seed: int, n_samples: int = 1, first_stream: int = 0, first_sample: int = 0,
+                     t_min: float | None = None, direct=None, records: bool = False):
+        """Direct lighting of n shading points [n, 6] {p, normal} (fields 1..6
+        of a hit_rays record) with n_samples light samples each: the f64 sums
+        [n, 3] of emitted * scattering_pdf / pdf over the samples s =
+        first_sample .. first_sample + n_samples - 1.  Per sample: the
+        direction, list index and pdf of light_sample (stream: seed,
+        first_stream + k, s), the closest hit of hit_rays along it, the
+        emission shade_rays gives that hit, and Lambertian's scattering pdf
+        max(dot(normal, unit(d)) / pi, 0); a term is added only for a hit with
+        pdf > 0 and scattering pdf > 0.  The light list's lobe alone, not the
+        reference's mixture; the caller multiplies by the albedo and divides by
+        the samples.  A point with normal (0, 0, 0) -- a miss row of hit_rays
+        -- is skipped: its sums stay as they are.  direct: sums to continue
+        ([n, 3] f64; updated in place when it is a contiguous f64 array or
+        tensor), or None to start from zero.  records=True also returns
+        (samples [n * n_samples, 12] {d, pdf, t, spdf, Le, term}, sample_ids
+        [n * n_samples, 4] int32 {light index, object id or -1, material id,
+        added}).  t_min defaults to f64::EPSILON.  numpy in, numpy out (the
+        host entry); torch GPU tensors go through the device entry on torch's
+        current stream."""
+        t_min = 2.220446049250313e-16 if t_min is None else float(t_min)
+        seed, n_samples, first_stream, first_sample = int(seed), int(n_samples), int(first_stream), int(first_sample)
+        np_dtype = np.float32 if self.precision == RTW_F32 else np.float64
+        accumulate = 0 if direct is None else 1
+        if type(points).__module__.split(".")[0] == "torch":
+            import torch
+            want = torch.float32 if self.precision == RTW_F32 else torch.float64
+            if points.dtype != want:
+                raise RenderError(_capi.RTW_E_INVALID, f"direct_light: tensor dtype {points.dtype}, the context's is {want}")
+            if not points.is_cuda or points.device.index != self.device:
+                raise RenderError(_capi.RTW_E_INVALID, f"direct_light: the tensor is not on device {self.device}")
+            if points.dim() != 2 or points.shape[1] != 6 or not points.is_contiguous():
+                raise RenderError(_capi.RTW_E_INVALID, "direct_light: points must be a contiguous [n, 6] tensor")
+            n = int(points.shape[0])
+            if direct is None:
+                direct = torch.zeros((n, 3), dtype=torch.float64, device=points.device)
+            elif type(direct).__module__.split(".")[0] != "torch" or direct.dtype != torch.float64 or \
+                    direct.device != points.device or tuple(direct.shape) != (n, 3) or not direct.is_contiguous():
+                raise RenderError(_capi.RTW_E_INVALID, "direct_light: direct must be a contiguous [n, 3] float64 "
+                                                       "tensor on the points' device")
+            rows = n * max(n_samples, 0)
+            samples = torch.zeros((rows, 12), dtype=want, device=points.device) if records else None
+            ids = torch.zeros((rows, 4), dtype=torch.int32, device=points.device) if records else None
+            stream = _torch_stream(self.device)
+            self._check(_lib.rtw_direct_light_device(
+                self.ctx, C.c_void_p(points.data_ptr()) if n else None, points.numel() * points.element_size(), n,
+                seed, first_stream, first_sample, n_samples, t_min, accumulate,
+                C.c_void_p(direct.data_ptr()) if n else None, direct.numel() * 8,
+                C.c_void_p(samples.data_ptr()) if records and rows else None,
+                samples.numel() * samples.element_size() if records else 0,
+                C.c_void_p(ids.data_ptr()) if records and rows else None, ids.numel() * 4 if records else 0,
+                C.c_void_p(stream) if stream else None), "rtw_direct_light_device")
+            return (direct, samples, ids) if records else direct
+        pts = np.ascontiguousarray(np.asarray(points, np_dtype))
+        if pts.ndim != 2 or pts.shape[1] != 6:
+            raise RenderError(_capi.RTW_E_INVALID, "direct_light: points must be [n, 6] {p, normal}")
+        n = int(pts.shape[0])
+        if direct is None:
+            direct = np.zeros((n, 3), np.float64)
+        else:
+            if not (isinstance(direct, np.ndarray) and direct.dtype == np.float64 and direct.flags.c_contiguous):
+                direct = np.ascontiguousarray(np.asarray(direct, np.float64))
+            if direct.shape != (n, 3):
+                raise RenderError(_capi.RTW_E_INVALID, "direct_light: direct must be [n, 3], one sum per point")
+        rows = n * max(n_samples, 0)
+        samples = np.zeros((rows, 12), np_dtype) if records else None
+        ids = np.zeros((rows, 4), np.int32) if records else None
+        self._check(_lib.rtw_direct_light(
+            self.ctx, pts.ctypes.data_as(C.c_void_p) if n else None, n, seed, first_stream, first_sample, n_samples,
+            t_min, accumulate, direct.ctypes.data_as(C.c_void_p) if n else None,
+            samples.ctypes.data_as(C.c_void_p) if records and rows else None,
+            ids.ctypes.data_as(C.c_void_p) if records and rows else None), "rtw_direct_light")
+        return (direct, samples, ids) if records else direct
+
+    def render_direct(self, cam: Camera, seed: int, light_samples: int = 1, first_sample: int = 0,
+                      n_samples: int | None = None, sums=None):
+        """One direct-light bounce of every pixel: [H, W, 3] f64 sums of
+        direct_light at the first hits of the camera samples first_sample ..
+        first_sample + n_samples - 1 (n_samples defaults to the camera's
+        samples_per_pixel), light_samples light samples at each.  Per camera
+        sample s: camera_rays, hit_rays, then direct_light on the records' {p,
+        normal} -- miss rows are skipped by the zero-normal rule -- with
+        first_stream 0 (the pixel index), first_sample s * light_samples, and
+        the seed seed ^ 0x9E3779B97F4A7C15, so the light draws do not reuse
+        the camera jitter's stream.  sums: [H, W, 3] f64 to continue (a
+        window's), or None.  The caller multiplies by the feature pass's albedo
+        and divides by the samples."""
+        W, H = int(cam.raw.image_width), int(cam.raw.image_height)
+        n_samples = int(cam.samples_per_pixel) if n_samples is None else int(n_samples)
+        light_samples, first_sample = int(light_samples), int(first_sample)
+        lseed = (int(seed) ^ 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+        if sums is None:
+            direct = None
+        else:
+            direct = np.ascontiguousarray(np.asarray(sums, np.float64)).reshape(-1, 3)
+            if direct.shape[0] != W * H:
+                raise RenderError(_capi.RTW_E_INVALID, "render_direct: sums must be [H, W, 3]")
+        for s in range(first_sample, first_sample + n_samples):
+            rays, _ = self.camera_rays(cam, seed, s)
+            hits, _ = self.hit_rays(rays)
+            direct = self.direct_light(np.ascontiguousarray(hits[:, 1:7]), lseed, light_samples, 0,
+                                       s * light_samples, direct=direct)
+        if direct is None:
+            direct = np.zeros((W * H, 3), np.float64)
+        return direct.reshape(H, W, 3)
 
     # ---- path queries: camera rays and the material bounce (rtw_camera_rays / rtw_shade_rays)
     @staticmethod

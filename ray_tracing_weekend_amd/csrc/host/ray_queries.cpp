@@ -93,6 +93,25 @@ LightSamples light_sample(const HittableList& world, const HittableList& lights,
     return out;
 }
 
+DirectLight direct_light(const HittableList& world, const HittableList& lights, const std::vector<double>& points,
+                         uint64_t seed, uint32_t n_samples, uint64_t first_stream, uint32_t first_sample, double t_min,
+                         bool records, const RenderOptions& opt) {
+    if (points.size() % 6) throw Error(RTW_E_INVALID, "direct_light: points holds 6 values per point");
+    const size_t n = points.size() / 6;
+    DirectLight out;
+    out.direct.resize(3 * n);
+    if (records) {
+        out.samples.resize(12 * n * n_samples);
+        out.sample_ids.resize(4 * n * n_samples);
+    }
+    rtw_ctx* ctx = query_context(world, lights, opt);
+    finish(ctx, rtw_direct_light(ctx, points.data(), n, seed, first_stream, first_sample, n_samples, t_min, 0,
+                                 out.direct.data(), records && !out.samples.empty() ? out.samples.data() : nullptr,
+                                 records && !out.sample_ids.empty() ? out.sample_ids.data() : nullptr),
+           "rtw_direct_light");
+    return out;
+}
+
 CameraRays camera_rays(const Camera& cam, uint64_t seed, uint32_t sample, const std::vector<uint32_t>& pixels,
                        uint64_t first_pixel, uint64_t n, const RenderOptions& opt) {
     if (opt.precision != RTW_F64) throw Error(RTW_E_INVALID, "the C++ mirror's ray queries are f64 (RTW_F64)");

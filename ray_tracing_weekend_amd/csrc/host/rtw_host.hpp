@@ -305,6 +305,18 @@ struct LightSamples {
 LightSamples light_sample(const HittableList& world, const HittableList& lights, const std::vector<double>& origins,
                           uint64_t seed, uint64_t first_stream = 0, uint32_t sample = 0, bool with_pdf = true,
                           const RenderOptions& opt = {});
+// Direct lighting of n points (6 values each {p, normal}; rtw_direct_light) with
+// n_samples light samples each: the sums of emitted * scattering_pdf / pdf over the
+// samples first_sample .. first_sample + n_samples - 1, point k drawing from the
+// stream of (seed, first_stream + k, s).  With records: the sample rows too.
+struct DirectLight {
+    std::vector<double> direct;       // 3 per point
+    std::vector<double> samples;      // 12 per (point, sample) {d, pdf, t, spdf, Le, term}, or empty
+    std::vector<int32_t> sample_ids;  // 4 per (point, sample) {light, object or -1, material, added}, or empty
+};
+DirectLight direct_light(const HittableList& world, const HittableList& lights, const std::vector<double>& points,
+                         uint64_t seed, uint32_t n_samples = 1, uint64_t first_stream = 0, uint32_t first_sample = 0,
+                         double t_min = 2.220446049250313e-16, bool records = false, const RenderOptions& opt = {});
 
 // Path queries (rtw_camera_rays / rtw_shade_rays, include/rtw.h), f64 on one
 // device; defined in host/ray_queries.cpp.
