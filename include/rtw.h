@@ -635,7 +635,10 @@ typedef struct rtw_query_stats {
                                      call); `kernel` is 0 for both; 8 direct lighting
                                      (rtw_direct_light: rays = the (point, sample) pairs traced,
                                      `hits` = the pairs that added a term, light_tests those
-                                     of the fused pdf, `kernel` is the world) */
+                                     of the fused pdf, `kernel` is the world), 9 ambient occlusion
+                                     (rtw_ambient_occlusion: rays = the (point, sample) pairs
+                                     traced, `hits` = the occluded pairs, `kernel` is the
+                                     world) */
     double kernel_ms;             /* device time of the query kernel (HIP events) */
 } rtw_query_stats;
 /* Counters of the last query (waits for it); RTW_E_INVALID before the first. */
@@ -770,6 +773,69 @@ int rtw_direct_light_device(rtw_ctx *ctx, const void *d_points, size_t points_by
                             uint64_t first_stream, uint32_t first_sample, uint32_t n_samples, double t_min,
                             int accumulate, double *d_direct, size_t direct_bytes, void *d_samples,
                             size_t samples_bytes, int32_t *d_sample_ids, size_t sample_ids_bytes, void *stream);
+
+/* ---- ambient occlusion as one query ----------------------------------------
+ * rtw_ambient_occlusion: for n shading points {p, normal} and S = n_samples
+ * samples each, how much of the cosine-weighted hemisphere above the point is
+ * open: the number of samples whose direction meets nothing.  With the
+ * reference's CosinePdf a sky sample's term is background * spdf / pdf =
+ * background, so the sky's share of a point's direct light is background *
+ * open / S -- the lobe rtw_direct_light (the light list's lobe alone) leaves
+ * out.  It fuses CosinePdf::generate and rtw_occluded_rays through the same
+ * device functions, on the same plan (world, test form, stack, LDS).  The
+ * answer is an integer count: exact in both precisions, and independent of the
+ * order the samples are taken in.
+ *
+ * The law, per point k, over s = first_sample .. first_sample + S - 1:
+ *   1. the stream Rng(seed, first_stream + k, s) -- rtw_light_sample's keying,
+ *      with `sample` = s; from its start, exactly the two draws of
+ *      CosinePdf::new(normal).generate(rng) (pdf.rs:38-52, onb.rs:8-35,
+ *      utils.rs:146-161): r1, r2 = two Standard f64 (in f32: their f32 form);
+ *   2. x = (cos(2 PI r1) sqrt(r2), sin(2 PI r1) sqrt(r2), sqrt(1 - r2));
+ *      Onb(normal): w = normalize(normal), a = |w.x| > 0.9 ? (0, 1, 0) : (1, 0, 0),
+ *      v = normalize(cross(w, a)), u = cross(w, v);
+ *      d = ((0 + u * x.x) + v * x.y) + w * x.z, the fold from zero of
+ *      Onb::transform.  In f64 this is the reference bit for bit; in f32 it is
+ *      the render's f32 form of the same operations.  d is not renormalised, so
+ *      t counts in units of |d|, which is 1 within rounding;
+ *   3. occ = world.hit(&{p, d}, t_min..=t_max).is_some(): rtw_occluded_rays of
+ *      {p, d} with that t_max bit for bit -- inclusive at both ends, a sphere's
+ *      far root when its near root is below t_min, the AABB gates of planes,
+ *      quads and cuboids over the range.  A NaN ray (a NaN normal or point)
+ *      answers 0.  t_max is one double for the call, rounded to the context's
+ *      precision; +inf is allowed; a t_max that is NaN or < t_min answers 0 for
+ *      every sample;
+ *   4. open[k] += !occ.
+ * A point whose normal is exactly (0, 0, 0) -- a miss row of rtw_hit_rays -- is
+ * skipped entirely: no draws, no traversal, its count 0 (untouched when
+ * accumulate != 0), its record rows 0.
+ *   points    : n x 6 {p xyz, normal xyz} in the context's precision: fields 1..6
+ *               of a rtw_hit_rays record
+ *   open      : n x uint32; overwritten, or continued from its content when
+ *               accumulate != 0, so windows over first_sample compose exactly
+ *   directions: optional (NULL), n * S x 3 in the context's precision, row
+ *               k * S + (s - first_sample): d
+ *   occluded  : optional (NULL), n * S bytes, the same rows: occ
+ * Calls compose over first_stream as rtw_light_sample's do.  Device form: each
+ * d_ pointer is followed by its size in bytes; d_points must be 16-byte aligned
+ * in f64 and 8-byte in f32, d_open 4-byte, d_directions 8-byte in f64 and 4-byte
+ * in f32; d_open is zeroed (unless accumulate) and added to on `stream`.
+ * Errors, checked in this order: RTW_E_INVALID for a NULL context;
+ * RTW_E_UNSUPPORTED on multi-device and virtual contexts; RTW_E_NO_SCENE before
+ * rtw_set_scene; RTW_E_INVALID for NULL points or open with n > 0, a t_min that
+ * is not finite and >= 0, n_samples == 0, n over 2^40, n * S over 2^62, n * S
+ * over 2^32 when a record is asked for, short or misaligned device buffers.  An
+ * empty light list is fine.  n = 0 launches nothing.  Query stats: is_light_pdf
+ * = 9, rays = the (point, sample) pairs traced, hits = the occluded pairs,
+ * kernel = the world that ran, node_visits and sphere_tests as in the any hit. */
+int rtw_ambient_occlusion(rtw_ctx *ctx, const void *points, uint64_t n, uint64_t seed, uint64_t first_stream,
+                          uint32_t first_sample, uint32_t n_samples, double t_min, double t_max, int accumulate,
+                          uint32_t *open, void *directions, uint8_t *occluded);
+int rtw_ambient_occlusion_device(rtw_ctx *ctx, const void *d_points, size_t points_bytes, uint64_t n, uint64_t seed,
+                                 uint64_t first_stream, uint32_t first_sample, uint32_t n_samples, double t_min,
+                                 double t_max, int accumulate, uint32_t *d_open, size_t open_bytes,
+                                 void *d_directions, size_t directions_bytes, uint8_t *d_occluded,
+                                 size_t occluded_bytes, void *stream);
 
 /* ---- path queries: camera rays and the material bounce ---------------------
  * The Material trait (shared/src/material.rs:32-49) and Camera::get_ray as

@@ -260,6 +260,20 @@ class HittableList:                          # hittable_collections/hittable_lis
             r.set_scene(flatten(self, lights))
             return r.direct_light(points, seed, n_samples, first_stream, first_sample, t_min, records=records)
 
+    def ambient_occlusion(self, points, seed: int, n_samples: int = 1, t_max: float | None = None,
+                          t_min: float | None = None, first_stream: int = 0, first_sample: int = 0, *,
+                          lights=None, records: bool = False, precision: int = RTW_F64, device: int = 0,
+                          accel: int = RTW_ACCEL_AUTO):
+        """The open counts of n points [n, 6] {p, normal} in this list as the
+        world (and the sample records) as Renderer.ambient_occlusion gives
+        them.  Stages the scene for this one call; keep a Renderer for repeated
+        queries."""
+        with Renderer(device=device, precision=precision) as r:
+            r.set_accel(accel)
+            r.set_scene(flatten(self, lights if lights is not None else HittableList()))
+            return r.ambient_occlusion(points, seed, n_samples, t_max, t_min, first_stream, first_sample,
+                                       records=records)
+
 
 class BoundedVolumeHierarchy(HittableList):  # hittable_collections/bvh.rs:106-143 (::from(list))
     """The reference's BVH over a list: as the world it gives the list's
@@ -1143,6 +1157,106 @@ class Renderer:
         if direct is None:
             direct = np.zeros((W * H, 3), np.float64)
         return direct.reshape(H, W, 3)
+
+    # ---- ambient occlusion as one query (rtw_ambient_occlusion)
+    def ambient_occlusion(self, points, seed: int, n_samples: int = 1, t_max: float | None = None,
+                          t_min: float | None = None, first_stream: int = 0, first_sample: int = 0, open=None,
+                          records: bool = False):
+        """How much of the cosine-weighted hemisphere above n shading points
+        [n, 6] {p, normal} (fields 1..6 of a hit_rays record) is open: uint32
+        [n], the number of the samples s = first_sample .. first_sample +
+        n_samples - 1 whose direction -- CosinePdf::generate in the normal's
+        frame, the first two draws of the stream (seed, first_stream + k, s) --
+        meets nothing over t_min..=t_max, as occluded answers that ray.  t_max:
+        one upper end for the call, None for +inf (the sky); NaN or below t_min
+        is an empty range, every sample open.  A point with normal (0, 0, 0) --
+        a miss row of hit_rays -- is skipped: its count stays as it is.  open:
+        counts to continue ([n] uint32; updated in place when it is a
+        contiguous uint32 array, or an int32 tensor holding those bits), or
+        None to start from zero, so sample windows compose exactly.
+        records=True also returns (directions [n * n_samples, 3], occluded
+        [n * n_samples] uint8), row k * n_samples + (s - first_sample).  t_min
+        defaults to f64::EPSILON.  numpy in, numpy out (the host entry); torch
+        GPU tensors go through the device entry on torch's current stream and
+        give the counts as an int32 tensor."""
+        t_min = 2.220446049250313e-16 if t_min is None else float(t_min)
+        t_max = float("inf") if t_max is None else float(t_max)
+        seed, n_samples, first_stream, first_sample = int(seed), int(n_samples), int(first_stream), int(first_sample)
+        np_dtype = np.float32 if self.precision == RTW_F32 else np.float64
+        accumulate = 0 if open is None else 1
+        if type(points).__module__.split(".")[0] == "torch":
+            import torch
+            want = torch.float32 if self.precision == RTW_F32 else torch.float64
+            if points.dtype != want:
+                raise RenderError(_capi.RTW_E_INVALID,
+                                  f"ambient_occlusion: tensor dtype {points.dtype}, the context's is {want}")
+            if not points.is_cuda or points.device.index != self.device:
+                raise RenderError(_capi.RTW_E_INVALID, f"ambient_occlusion: the tensor is not on device {self.device}")
+            if points.dim() != 2 or points.shape[1] != 6 or not points.is_contiguous():
+                raise RenderError(_capi.RTW_E_INVALID, "ambient_occlusion: points must be a contiguous [n, 6] tensor")
+            n = int(points.shape[0])
+            if open is None:
+                open = torch.zeros((n,), dtype=torch.int32, device=points.device)
+            elif type(open).__module__.split(".")[0] != "torch" or open.dtype != torch.int32 or \
+                    open.device != points.device or tuple(open.shape) != (n,) or not open.is_contiguous():
+                raise RenderError(_capi.RTW_E_INVALID, "ambient_occlusion: open must be a contiguous [n] int32 "
+                                                       "tensor on the points' device")
+            rows = n * max(n_samples, 0)
+            dirs = torch.zeros((rows, 3), dtype=want, device=points.device) if records else None
+            occ = torch.zeros((rows,), dtype=torch.uint8, device=points.device) if records else None
+            stream = _torch_stream(self.device)
+            self._check(_lib.rtw_ambient_occlusion_device(
+                self.ctx, C.c_void_p(points.data_ptr()) if n else None, points.numel() * points.element_size(), n,
+                seed, first_stream, first_sample, n_samples, t_min, t_max, accumulate,
+                C.c_void_p(open.data_ptr()) if n else None, open.numel() * 4,
+                C.c_void_p(dirs.data_ptr()) if records and rows else None,
+                dirs.numel() * dirs.element_size() if records else 0,
+                C.c_void_p(occ.data_ptr()) if records and rows else None, occ.numel() if records else 0,
+                C.c_void_p(stream) if stream else None), "rtw_ambient_occlusion_device")
+            return (open, dirs, occ) if records else open
+        pts = np.ascontiguousarray(np.asarray(points, np_dtype))
+        if pts.ndim != 2 or pts.shape[1] != 6:
+            raise RenderError(_capi.RTW_E_INVALID, "ambient_occlusion: points must be [n, 6] {p, normal}")
+        n = int(pts.shape[0])
+        if open is None:
+            open = np.zeros(n, np.uint32)
+        else:
+            if not (isinstance(open, np.ndarray) and open.dtype == np.uint32 and open.flags.c_contiguous):
+                open = np.ascontiguousarray(np.asarray(open, np.uint32))
+            if open.shape != (n,):
+                raise RenderError(_capi.RTW_E_INVALID, "ambient_occlusion: open must be [n], one count per point")
+        rows = n * max(n_samples, 0)
+        dirs = np.zeros((rows, 3), np_dtype) if records else None
+        occ = np.zeros(rows, np.uint8) if records else None
+        self._check(_lib.rtw_ambient_occlusion(
+            self.ctx, pts.ctypes.data_as(C.c_void_p) if n else None, n, seed, first_stream, first_sample, n_samples,
+            t_min, t_max, accumulate, open.ctypes.data_as(C.c_void_p) if n else None,
+            dirs.ctypes.data_as(C.c_void_p) if records and rows else None,
+            occ.ctypes.data_as(C.c_void_p) if records and rows else None), "rtw_ambient_occlusion")
+        return (open, dirs, occ) if records else open
+
+    def render_ao(self, cam: Camera, seed: int, ao_samples: int = 1, t_max: float | None = None):
+        """An ambient-occlusion pass of every pixel: ([H, W] uint32 open, [H, W]
+        uint32 taken).  Per camera sample s of the camera's samples_per_pixel:
+        camera_rays, hit_rays, then ambient_occlusion on the records' {p,
+        normal} with first_stream 0 (the pixel index), first_sample s *
+        ao_samples, and the seed seed ^ 0x9E3779B97F4A7C15 (render_direct's),
+        so the draws do not reuse the camera jitter's stream.  A miss row takes
+        nothing: its zero normal is skipped, and `taken` counts ao_samples for
+        every first hit.  open / taken is the pixel's open share; with t_max
+        None it is the sky's."""
+        W, H = int(cam.raw.image_width), int(cam.raw.image_height)
+        ao_samples = int(ao_samples)
+        aseed = (int(seed) ^ 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+        open_ = np.zeros(W * H, np.uint32)
+        taken = np.zeros(W * H, np.uint32)
+        for s in range(int(cam.samples_per_pixel)):
+            rays, _ = self.camera_rays(cam, seed, s)
+            hits, _ = self.hit_rays(rays)
+            pts = np.ascontiguousarray(hits[:, 1:7])
+            open_ = self.ambient_occlusion(pts, aseed, ao_samples, t_max, None, 0, s * ao_samples, open=open_)
+            taken += np.where((pts[:, 3:6] != 0).any(-1), ao_samples, 0).astype(np.uint32)
+        return open_.reshape(H, W), taken.reshape(H, W)
 
     # ---- path queries: camera rays and the material bounce (rtw_camera_rays / rtw_shade_rays)
     @staticmethod

@@ -112,6 +112,26 @@ DirectLight direct_light(const HittableList& world, const HittableList& lights, 
     return out;
 }
 
+AmbientOcclusion ambient_occlusion(const HittableList& world, const HittableList& lights,
+                                   const std::vector<double>& points, uint64_t seed, uint32_t n_samples, double t_max,
+                                   double t_min, uint64_t first_stream, uint32_t first_sample, bool records,
+                                   const RenderOptions& opt) {
+    if (points.size() % 6) throw Error(RTW_E_INVALID, "ambient_occlusion: points holds 6 values per point");
+    const size_t n = points.size() / 6;
+    AmbientOcclusion out;
+    out.open.resize(n);
+    if (records) {
+        out.directions.resize(3 * n * n_samples);
+        out.occluded.resize(n * n_samples);
+    }
+    rtw_ctx* ctx = query_context(world, lights, opt);
+    finish(ctx, rtw_ambient_occlusion(ctx, points.data(), n, seed, first_stream, first_sample, n_samples, t_min, t_max,
+                                      0, out.open.data(), records && !out.directions.empty() ? out.directions.data() : nullptr,
+                                      records && !out.occluded.empty() ? out.occluded.data() : nullptr),
+           "rtw_ambient_occlusion");
+    return out;
+}
+
 CameraRays camera_rays(const Camera& cam, uint64_t seed, uint32_t sample, const std::vector<uint32_t>& pixels,
                        uint64_t first_pixel, uint64_t n, const RenderOptions& opt) {
     if (opt.precision != RTW_F64) throw Error(RTW_E_INVALID, "the C++ mirror's ray queries are f64 (RTW_F64)");

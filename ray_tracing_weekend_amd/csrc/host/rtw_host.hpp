@@ -20,6 +20,7 @@
 
 #include <array>
 #include <functional>
+#include <limits>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -317,6 +318,20 @@ struct DirectLight {
 DirectLight direct_light(const HittableList& world, const HittableList& lights, const std::vector<double>& points,
                          uint64_t seed, uint32_t n_samples = 1, uint64_t first_stream = 0, uint32_t first_sample = 0,
                          double t_min = 2.220446049250313e-16, bool records = false, const RenderOptions& opt = {});
+// Ambient occlusion of n points (6 values each {p, normal}; rtw_ambient_occlusion)
+// with n_samples cosine-lobe samples each: how many of the samples first_sample ..
+// first_sample + n_samples - 1 meet nothing over t_min..=t_max, point k drawing
+// from the stream of (seed, first_stream + k, s).  With records: the sample rows too.
+struct AmbientOcclusion {
+    std::vector<uint32_t> open;       // 1 per point
+    std::vector<double> directions;   // 3 per (point, sample), or empty
+    std::vector<uint8_t> occluded;    // 1 per (point, sample), or empty
+};
+AmbientOcclusion ambient_occlusion(const HittableList& world, const HittableList& lights,
+                                   const std::vector<double>& points, uint64_t seed, uint32_t n_samples = 1,
+                                   double t_max = std::numeric_limits<double>::infinity(),
+                                   double t_min = 2.220446049250313e-16, uint64_t first_stream = 0,
+                                   uint32_t first_sample = 0, bool records = false, const RenderOptions& opt = {});
 
 // Path queries (rtw_camera_rays / rtw_shade_rays, include/rtw.h), f64 on one
 // device; defined in host/ray_queries.cpp.
