@@ -638,7 +638,9 @@ typedef struct rtw_query_stats {
                                      of the fused pdf, `kernel` is the world), 9 ambient occlusion
                                      (rtw_ambient_occlusion: rays = the (point, sample) pairs
                                      traced, `hits` = the occluded pairs, `kernel` is the
-                                     world) */
+                                     world), 10 radiance (rtw_radiance_rays: rays = the
+                                     segments traced, `hits` = the SCATTER events, light_tests
+                                     those of the bounces' pdfs, `kernel` is the world) */
     double kernel_ms;             /* device time of the query kernel (HIP events) */
 } rtw_query_stats;
 /* Counters of the last query (waits for it); RTW_E_INVALID before the first. */
@@ -836,6 +838,78 @@ int rtw_ambient_occlusion_device(rtw_ctx *ctx, const void *d_points, size_t poin
                                  double t_max, int accumulate, uint32_t *d_open, size_t open_bytes,
                                  void *d_directions, size_t directions_bytes, uint8_t *d_occluded,
                                  size_t occluded_bytes, void *stream);
+
+/* ---- radiance along arbitrary rays as one query -----------------------------
+ * rtw_radiance_rays: for n rays {origin, direction} and S = n_samples samples
+ * each, the full incoming radiance: Camera::ray_colour_tail_call
+ * (camera.rs:460-522) run to the end of every path, the sample colours summed
+ * in f64.  It fuses the loop of rtw_hit_rays, rtw_shade_rays and
+ * rtw_path_advance into one kernel through the same device functions, on the
+ * same plan (world, test form, stacks, LDS, light path, tuning keys): no record
+ * of a round leaves the registers.  With rtw_direct_light (the light list's
+ * lobe) and rtw_ambient_occlusion (the sky's) this is the third fused
+ * estimator: everything.
+ *
+ * The law, per ray k, over s = first_sample .. first_sample + S - 1 in that
+ * order:
+ *   1. the stream.  rng == NULL: Rng(seed, first_stream + k, s) from its start
+ *      -- rtw_light_sample's keying, with `sample` = s.  rng != NULL: n x 4
+ *      uint64 start states and n_samples must be 1; rng[k] is read (four zero
+ *      words are no xoshiro256++ state: as in rtw_shade_rays the stream of (0,
+ *      0, 0) stands in from the path's first hit on, and a path that never hits
+ *      leaves them as they are) and written back after the path.  So
+ *      rtw_camera_rays followed by rtw_radiance_rays(rng) is one sample of
+ *      Camera::render;
+ *   2. the path.  mult = (1, 1, 1), res = 0, r = rays[k]; up to max_depth
+ *      rounds of: the record of rtw_hit_rays(r, t_min = f64::EPSILON); next,
+ *      weight, emitted and event of rtw_shade_rays on that record, the stream
+ *      advanced by exactly its draws; then rtw_path_advance's bookkeeping, every
+ *      product rounded before its add:
+ *        MISS      colour = mult * background + res, the path ends
+ *        ABSORBED  colour = mult * emitted + res, the path ends
+ *        SCATTER   res += mult * emitted; mult *= weight; r = next
+ *        REFLECT   mult *= weight; r = next
+ *      a path alive after max_depth rounds ends with colour = 0 + res; with
+ *      max_depth == 0 every colour is 0 + 0 and nothing is traced.  background
+ *      is three doubles, rounded to the context's precision.  Every field is
+ *      those queries' bit for bit in each precision (f32: the plain f32
+ *      arithmetic of the f32 queries);
+ *   3. the fold.  radiance[k][c] += (double)colour_c: one f64 add per sample, in
+ *      sample order, never contracted.  NaN is not scrubbed (the tail-call form
+ *      never calls fix_nan).
+ *   rays     : n x 6 {origin xyz, direction xyz} in the context's precision, as
+ *              for rtw_hit_rays
+ *   radiance : n x 3 f64 in both precisions; overwritten, or continued from its
+ *              content when accumulate != 0, so windows over first_sample compose
+ *              exactly
+ *   colours  : optional (NULL), n * S x 3 in the context's precision, row
+ *              k * S + (s - first_sample): the sample's colour
+ *   segments : optional (NULL), n * S uint32, the same rows: the world.hit calls
+ *              of the pair
+ * Calls compose over first_stream as rtw_light_sample's do.  Device form: each
+ * d_ pointer is followed by its size in bytes; d_rays must be 16-byte aligned in
+ * f64 and 8-byte in f32, d_radiance 8-byte, d_rng 16-byte, d_colours 8-byte in
+ * f64 and 4-byte in f32, d_segments 4-byte; `stream` as for
+ * rtw_direct_light_device.
+ * Errors, checked in this order before any device call: RTW_E_INVALID for a NULL
+ * context; RTW_E_UNSUPPORTED on multi-device and virtual contexts;
+ * RTW_E_NO_SCENE before rtw_set_scene; RTW_E_NO_LIGHTS where rtw_shade_rays
+ * gives it (an empty light list and a Lambertian material); RTW_E_INVALID for
+ * NULL rays, radiance or background with n > 0, n_samples == 0, rng with
+ * n_samples != 1, first_sample + n_samples over 2^32, n over 2^40, n * S over
+ * 2^62, n * S over 2^32 when a record is asked for, short or misaligned device
+ * buffers.  n = 0 launches nothing.  Query stats: is_light_pdf = 10, rays = the
+ * segments traced, hits = the SCATTER events, kernel = the world that ran,
+ * light_tests, node_visits and sphere_tests as in the closest hit and the
+ * bounce. */
+int rtw_radiance_rays(rtw_ctx *ctx, const void *rays, uint64_t n, uint64_t seed, uint64_t first_stream,
+                      uint32_t first_sample, uint32_t n_samples, uint32_t max_depth, const double background[3],
+                      uint64_t *rng, int accumulate, double *radiance, void *colours, uint32_t *segments);
+int rtw_radiance_rays_device(rtw_ctx *ctx, const void *d_rays, size_t rays_bytes, uint64_t n, uint64_t seed,
+                             uint64_t first_stream, uint32_t first_sample, uint32_t n_samples, uint32_t max_depth,
+                             const double background[3], uint64_t *d_rng, size_t rng_bytes, int accumulate,
+                             double *d_radiance, size_t radiance_bytes, void *d_colours, size_t colours_bytes,
+                             uint32_t *d_segments, size_t segments_bytes, void *stream);
 
 /* ---- path queries: camera rays and the material bounce ---------------------
  * The Material trait (shared/src/material.rs:32-49) and Camera::get_ray as

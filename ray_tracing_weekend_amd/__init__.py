@@ -274,6 +274,19 @@ class HittableList:                          # hittable_collections/hittable_lis
             return r.ambient_occlusion(points, seed, n_samples, t_max, t_min, first_stream, first_sample,
                                        records=records)
 
+    def radiance(self, rays, seed: int, n_samples: int = 1, max_depth: int = 50, background=(0.0, 0.0, 0.0),
+                 first_stream: int = 0, first_sample: int = 0, *, lights, records: bool = False,
+                 precision: int = RTW_F64, device: int = 0, accel: int = RTW_ACCEL_AUTO):
+        """Incoming radiance along n rays [n, 6] {origin, direction} in this list
+        as the world, with the light list `lights`: the sums [n, 3] (and the
+        sample records) as Renderer.radiance gives them.  Stages the scene for
+        this one call; keep a Renderer for repeated queries."""
+        with Renderer(device=device, precision=precision) as r:
+            r.set_accel(accel)
+            r.set_scene(flatten(self, lights))
+            return r.radiance(rays, seed, n_samples, max_depth, background, first_stream, first_sample,
+                              records=records)
+
 
 class BoundedVolumeHierarchy(HittableList):  # hittable_collections/bvh.rs:106-143 (::from(list))
     """The reference's BVH over a list: as the world it gives the list's
@@ -1257,6 +1270,104 @@ class Renderer:
             open_ = self.ambient_occlusion(pts, aseed, ao_samples, t_max, None, 0, s * ao_samples, open=open_)
             taken += np.where((pts[:, 3:6] != 0).any(-1), ao_samples, 0).astype(np.uint32)
         return open_.reshape(H, W), taken.reshape(H, W)
+
+    # ---- radiance along arbitrary rays as one query (rtw_radiance_rays)
+    def radiance(self, rays, seed: int, n_samples: int = 1, max_depth: int = 50, background=(0.0, 0.0, 0.0),
+                 first_stream: int = 0, first_sample: int = 0, rng=None, radiance=None, records: bool = False):
+        """Incoming radiance along n rays [n, 6] {origin, direction}: the f64
+        sums [n, 3] of the sample colours s = first_sample .. first_sample +
+        n_samples - 1, each Camera::ray_colour_tail_call run to the end of its
+        path -- up to max_depth rounds of hit_rays(t_min = f64::EPSILON),
+        shade_rays and path_advance's fold, in one kernel.  MISS ends a path
+        with mult * background + res, ABSORBED with mult * emitted + res, a
+        path alive after max_depth rounds with 0 + res.  Sample s of ray k
+        draws from the stream (seed, first_stream + k, s), light_sample's
+        keying; with rng ([n, 4] start states, numpy uint64 or a torch int64
+        tensor carrying those bits; n_samples must be 1) from the caller's
+        state, which is UPDATED IN PLACE -- camera_rays followed by
+        radiance(rng=rng) is one sample of a render.  radiance: sums to
+        continue ([n, 3] f64; updated in place when it is a contiguous f64
+        array or tensor), or None to start from zero, so sample windows
+        compose exactly.  NaN is not scrubbed.  records=True also returns
+        (colours [n * n_samples, 3] of the context's precision, segments [n *
+        n_samples] -- the world.hit calls of the pair; uint32, int32 as a
+        tensor), row k * n_samples + (s - first_sample).  numpy in, numpy out
+        (the host entry); torch GPU tensors go through the device entry on
+        torch's current stream."""
+        seed, n_samples, max_depth = int(seed), int(n_samples), int(max_depth)
+        first_stream, first_sample = int(first_stream), int(first_sample)
+        bg = (C.c_double * 3)(*[float(v) for v in background])
+        accumulate = 0 if radiance is None else 1
+        r, is_torch = self._query_rays(rays, "radiance")
+        n = int(r.shape[0])
+        rows = n * max(n_samples, 0)
+        if is_torch:
+            import torch
+            if radiance is None:
+                radiance = torch.zeros((n, 3), dtype=torch.float64, device=r.device)
+            elif type(radiance).__module__.split(".")[0] != "torch" or radiance.dtype != torch.float64 or \
+                    radiance.device != r.device or tuple(radiance.shape) != (n, 3) or not radiance.is_contiguous():
+                raise RenderError(_capi.RTW_E_INVALID, "radiance: radiance must be a contiguous [n, 3] float64 "
+                                                       "tensor on the rays' device")
+            if rng is not None and (type(rng).__module__.split(".")[0] != "torch" or rng.dtype != torch.int64 or
+                                    rng.device != r.device or tuple(rng.shape) != (n, 4) or not rng.is_contiguous()):
+                raise RenderError(_capi.RTW_E_INVALID, "radiance: rng must be a contiguous [n, 4] int64 tensor on "
+                                                       "the rays' device")
+            colours = torch.zeros((rows, 3), dtype=r.dtype, device=r.device) if records else None
+            segs = torch.zeros((rows,), dtype=torch.int32, device=r.device) if records else None
+            stream = _torch_stream(self.device)
+            self._check(_lib.rtw_radiance_rays_device(
+                self.ctx, C.c_void_p(r.data_ptr()) if n else None, r.numel() * r.element_size(), n, seed,
+                first_stream, first_sample, n_samples, max_depth, bg,
+                C.c_void_p(rng.data_ptr()) if rng is not None and n else None, rng.numel() * 8 if rng is not None else 0,
+                accumulate, C.c_void_p(radiance.data_ptr()) if n else None, radiance.numel() * 8,
+                C.c_void_p(colours.data_ptr()) if records and rows else None,
+                colours.numel() * colours.element_size() if records else 0,
+                C.c_void_p(segs.data_ptr()) if records and rows else None, segs.numel() * 4 if records else 0,
+                C.c_void_p(stream) if stream else None), "rtw_radiance_rays_device")
+            return (radiance, colours, segs) if records else radiance
+        if radiance is None:
+            radiance = np.zeros((n, 3), np.float64)
+        else:
+            if not (isinstance(radiance, np.ndarray) and radiance.dtype == np.float64 and radiance.flags.c_contiguous):
+                radiance = np.ascontiguousarray(np.asarray(radiance, np.float64))
+            if radiance.shape != (n, 3):
+                raise RenderError(_capi.RTW_E_INVALID, "radiance: radiance must be [n, 3], one sum per ray")
+        if rng is not None and (not isinstance(rng, np.ndarray) or rng.dtype != np.uint64 or rng.shape != (n, 4) or
+                                not rng.flags.c_contiguous or not rng.flags.writeable):
+            raise RenderError(_capi.RTW_E_INVALID, "radiance: rng must be a writeable C-contiguous [n, 4] uint64 array "
+                                                   "(it is updated in place)")
+        colours = np.zeros((rows, 3), r.dtype) if records else None
+        segs = np.zeros(rows, np.uint32) if records else None
+        self._check(_lib.rtw_radiance_rays(
+            self.ctx, r.ctypes.data_as(C.c_void_p) if n else None, n, seed, first_stream, first_sample, n_samples,
+            max_depth, bg, rng.ctypes.data_as(C.c_void_p) if rng is not None and n else None, accumulate,
+            radiance.ctypes.data_as(C.c_void_p) if n else None,
+            colours.ctypes.data_as(C.c_void_p) if records and rows else None,
+            segs.ctypes.data_as(C.c_void_p) if records and rows else None), "rtw_radiance_rays")
+        return (radiance, colours, segs) if records else radiance
+
+    def render_radiance(self, cam: Camera, seed: int, first_sample: int = 0, n_samples: int | None = None, sums=None):
+        """The camera's image through the radiance query: [H, W, 3] f64 sums of
+        the samples first_sample .. first_sample + n_samples - 1 of every pixel
+        (n_samples defaults to the camera's samples from first_sample on).  Per
+        camera sample s: camera_rays, then radiance(rng=rng) with the camera's
+        max_depth and background, folded in sample order -- in RTW_F64 the sums
+        are render()'s at chunk 1 bit for bit.  sums: [H, W, 3] f64 to continue
+        (a window's), or None."""
+        W, H = int(cam.raw.image_width), int(cam.raw.image_height)
+        first_sample = int(first_sample)
+        n_samples = max(int(cam.raw.samples_per_pixel) - first_sample, 0) if n_samples is None else int(n_samples)
+        if sums is None:
+            acc = np.zeros((W * H, 3), np.float64)
+        else:
+            acc = np.array(sums, np.float64).reshape(-1, 3)
+            if acc.shape[0] != W * H:
+                raise RenderError(_capi.RTW_E_INVALID, "render_radiance: sums must be [H, W, 3]")
+        for s in range(first_sample, first_sample + n_samples):
+            rays, rng = self.camera_rays(cam, seed, s)
+            acc = self.radiance(rays, seed, 1, int(cam.raw.max_depth), cam.background, rng=rng, radiance=acc)
+        return acc.reshape(H, W, 3)
 
     # ---- path queries: camera rays and the material bounce (rtw_camera_rays / rtw_shade_rays)
     @staticmethod

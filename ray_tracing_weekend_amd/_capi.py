@@ -192,6 +192,13 @@ PROTOTYPES = [
                                                C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_int, C.c_void_p,
                                                C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                                C.c_void_p]),
+    ("rtw_radiance_rays", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                    C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.c_void_p, C.c_int, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
+    ("rtw_radiance_rays_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64,
+                                           C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.c_void_p,
+                                           C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                           C.c_void_p, C.c_size_t, C.c_void_p]),
     ("rtw_camera_rays", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64,
                                   C.c_uint64, C.c_void_p, C.c_void_p]),
     ("rtw_camera_rays_device", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32, C.c_void_p,
