@@ -469,6 +469,46 @@ int rtw_render_adaptive_image_device(rtw_ctx *ctx, const rtw_camera *cam, uint64
 int rtw_render_window_image(rtw_ctx *ctx, const rtw_camera *cam, uint64_t seed,
                             uint32_t first_sample, uint32_t n_samples,
                             double *sums, rtw_stats *stats);
+/* ---- per-pixel luminance moments: the variance guide of a denoiser ---------
+ * moments is always f64 [H, W, 2] = {S1, S2} in image order, j = 0 the bottom
+ * row: with Y = ((0.2126 r) + (0.7152 g)) + (0.0722 b) of each sample's colour
+ * (widened exactly when the context is f32), S1 = sum Y and S2 = sum Y * Y in
+ * sample order, every operation a separately rounded f64 operation -- the
+ * statistic of the adaptive fold above. */
+/* rtw_render_window that also keeps the moments: samples [first_sample,
+ * first_sample + n_samples) of every pixel, one sample per item, folded in
+ * sample order onto sums (H*W*3 doubles, image order; rtw_render_window's
+ * additions at chunk 1, bit for bit) and onto moments (H*W*2 doubles).  Both
+ * are read when first_sample > 0 and ignored when it is 0, so windows [0, a),
+ * [a, b), ... give the call of [0, b) bit for bit, in both precisions.  A
+ * window larger than the chunk-sum budget runs in sub-windows internally; the
+ * result does not depend on where they fall, nor on tuning tile_cull (a moments
+ * window does not cull).  cam->samples_per_pixel and the tuning key "window"
+ * are not read.  n_samples == 0 and an image without pixels do nothing.
+ * RTW_E_INVALID (nothing launched): a NULL context, camera, sums or moments,
+ * first_sample + n_samples beyond 2^32 - 1, an explicit rtw_set_chunk above 1,
+ * (device form) a buffer that is too small; RTW_E_UNSUPPORTED on a multi-device
+ * or virtual-rank context and for a width or height of 2^16 or more;
+ * RTW_E_NO_SCENE.  Stats are the window's, chunk = 1.  The host form is
+ * synchronous; the device form takes device memory of the context's device,
+ * runs on `stream` and waits for the device only where rtw_render_window_device
+ * does. */
+int rtw_render_window_moments(rtw_ctx *ctx, const rtw_camera *cam, uint64_t seed,
+                              uint32_t first_sample, uint32_t n_samples,
+                              double *sums, double *moments, rtw_stats *stats);
+int rtw_render_window_moments_device(rtw_ctx *ctx, const rtw_camera *cam, uint64_t seed,
+                                     uint32_t first_sample, uint32_t n_samples,
+                                     double *d_sums, size_t sums_bytes,
+                                     double *d_moments, size_t moments_bytes, void *stream);
+/* The {S1, S2} of the last rtw_render_adaptive / rtw_render_adaptive_device of
+ * this one-device context, at that render's image size: per pixel the sums over
+ * its first counts[pixel] samples.  RTW_E_INVALID before any adaptive render on
+ * the context, after rtw_set_scene, for NULL or (device form) too-small
+ * moments; RTW_E_UNSUPPORTED on a multi-device or virtual-rank context.  The
+ * host form is synchronous; the device form enqueues one copy kernel on
+ * `stream` and never waits (the caller orders it after the adaptive render). */
+int rtw_adaptive_moments(rtw_ctx *ctx, double *moments);
+int rtw_adaptive_moments_device(rtw_ctx *ctx, double *d_moments, size_t bytes, void *stream);
 uint32_t rtw_tile_size(void);                        /* tile edge in pixels (8) */
 uint32_t rtw_tiles_for_rank(uint32_t image_width, uint32_t image_height, uint32_t rank,
                             uint32_t nranks);
@@ -1245,8 +1285,71 @@ typedef struct rtw_denoise_stats {
     uint64_t left_nonfinite;      /* pixels whose output has a non-finite channel */
     double kernel_ms;             /* device time of the whole pass (HIP events) */
 } rtw_denoise_stats;
-/* Counters of the last denoise (waits for it); RTW_E_INVALID before the first. */
+/* Counters of the last denoise -- rtw_denoise or rtw_denoise_variance -- (waits
+ * for it); RTW_E_INVALID before the first. */
 int rtw_get_denoise_stats(rtw_ctx *ctx, rtw_denoise_stats *stats);
+
+/* ---- variance-guided denoising: the colour stop scaled by each pixel's noise --
+ * rtw_denoise's filter with another colour stop: instead of a fixed width it
+ * has the width of the centre pixel's own standard error, from the luminance
+ * moments {S1, S2} of the render (rtw_render_window_moments,
+ * rtw_adaptive_moments), and the variance is filtered along with the colour
+ * from iteration to iteration (the SVGF scheme).  A converged pixel is left
+ * alone; a noisy one is smoothed.  moments: [H, W, 2] f64, image order.
+ *
+ * Everything not written here is rtw_denoise's contract verbatim: guide_ok,
+ * valid, c, the demodulation floor 2^-10, a, e, N, d, w_n, w_d, h, the tap
+ * order (dy outer, dx inner), the skipped taps, the fill, the finish.  Every
+ * operation is one separately rounded f64 operation in the written order, and
+ * "x > y ? x : y" is that comparison and select.
+ * Prepare, additionally, with nd = (double)n:
+ *   m = S1 / nd;  q = S2 / nd;  var = q - m*m;  var = var > 0 ? var : 0;
+ *   v = var / (nd - 1)                      (the variance of the mean luminance)
+ *   aY = ((0.2126 a0) + (0.7152 a1)) + (0.0722 a2)   (1 when demodulate == 0)
+ *   ve = v / (aY * aY)                      (... of the irradiance's luminance)
+ *   has_var = valid and n > 1 and S1, S2 finite and ve finite; otherwise ve = 0.
+ *   (S1 and S2 are asked by themselves: a NaN var would pass the select as 0.)
+ *   has_var never changes afterwards: a pixel that is filled later keeps
+ *   has_var = false and ve = 0.
+ * Iteration k = 0 .. iterations - 1, step = 2^k.  sv2 = sigma_var * sigma_var
+ * (on the host), eps = 2^-40.  For a centre p: thr = sv2 * ve_p + eps and
+ * Ye_p = ((0.2126 e0) + (0.7152 e1)) + (0.0722 e2) of the colour the iteration
+ * reads.  Per tap q that is a source:
+ *   g = Ye_p - Ye_q;  s = g * g;  w_c = has_var_p ? 1 / (1 + s / thr) : 1
+ *   w = (((h[dy+2] * h[dx+2]) * w_n) * w_d) * w_c
+ *   num_k = num_k + w * eq_k;  den = den + w;  vnum = vnum + (w * w) * ve_q
+ * After the taps a centre that takes e' = num / den also takes ve' = vnum /
+ * (den * den) when has_var; otherwise its ve stays.  The stop is not shrunk by
+ * 2^-k: the filtered variance does that.  sigma_var = 0 is allowed (thr = eps).
+ * A frame in which no pixel has has_var (every count 1, say) is rtw_denoise
+ * with sigma_colour = 0, bit for bit.
+ *
+ * counts, params, sums_precision, the device, the buffers and tuning key
+ * denoise_lds are rtw_denoise's (the staged form keeps 80 bytes per pixel of
+ * the tile and its halo, so it fits up to step 4).  Errors: rtw_denoise's, with
+ * sigma_var negative, infinite or NaN in place of sigma_colour, and a NULL,
+ * too-small, misaligned or overlapped moments array.  rtw_get_denoise_stats
+ * reports the call. */
+typedef struct rtw_denoise_variance_params {
+    uint32_t iterations;          /* 1..16 */
+    uint32_t normal_power_log2;   /* 0..10 */
+    double sigma_var;             /* >= 0: the colour stop's width in standard errors of the centre */
+    double sigma_depth;           /* > 0 */
+    uint32_t demodulate;          /* 1: filter colour / first-hit albedo */
+    uint32_t fill_nonfinite;      /* 1: non-finite pixels take their neighbours' filtered colour */
+} rtw_denoise_variance_params;
+/* iterations 5, normal_power_log2 5, sigma_var 2.0, sigma_depth 0.125, demodulate 1, fill_nonfinite 1 */
+void rtw_denoise_variance_params_default(rtw_denoise_variance_params *out);
+int rtw_denoise_variance(rtw_ctx *ctx, const double *sums, const double *features, const double *moments,
+                         const uint32_t *counts, uint32_t spp, uint32_t width, uint32_t height,
+                         const rtw_denoise_variance_params *params, double *out);
+int rtw_denoise_variance_device(rtw_ctx *ctx, const void *d_sums, int sums_precision, size_t sums_bytes,
+                                const double *d_features, size_t features_bytes,
+                                const double *d_moments, size_t moments_bytes,
+                                const uint32_t *d_counts, size_t counts_bytes,
+                                uint32_t spp, uint32_t width, uint32_t height,
+                                const rtw_denoise_variance_params *params,
+                                double *d_out, size_t out_bytes, void *stream);
 
 /* ---- scenes::simple (scenes/src/lib.rs:155-233) ----------------------- */
 /* The library owns the arrays; view them through rtw_world_scene(). grid_n =

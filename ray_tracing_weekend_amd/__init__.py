@@ -32,7 +32,7 @@ __all__ = [
     "Quad", "Cuboid", "Transformation", "translation", "rotation", "SolidColour", "CheckerTexture",
     "NoiseTexture", "Perlin", "HittableList", "BoundedVolumeHierarchy", "SceneSoA", "flatten",
     "CameraBuilder", "Camera", "Renderer", "scenes", "encode_rgb8", "write_ppm", "RenderError",
-    "RTW_F32", "RTW_F64", "feature_means", "DenoiseParams",
+    "RTW_F32", "RTW_F64", "feature_means", "DenoiseParams", "DenoiseVarianceParams",
 ]
 
 _lib = _capi.load()   # raises if librtw.so is missing: there is no CPU fallback
@@ -630,14 +630,22 @@ class Camera:
             return r.render_wavefront_batched(self, seed, first_sample, n_samples, batch=batch, on_bounce=on_bounce)
 
     def render_denoised(self, world, lights, *, seed: int = 0x5EED0001, precision: int = RTW_F64, device: int = 0,
-                        accel: int = RTW_ACCEL_AUTO, **params) -> np.ndarray:
+                        accel: int = RTW_ACCEL_AUTO, variance: bool = False, **params) -> np.ndarray:
         """The render, its feature pass and the denoiser on one context: the
         filtered per-sample means [H, W, 3] float64 of Renderer.render's sums
         and Renderer.render_features' guides of the same samples (display them
-        with spp = 1).  **params as Renderer.denoise's."""
+        with spp = 1).  **params as Renderer.denoise's.  variance=True: the
+        variance-guided filter instead -- Renderer.render_window_moments of
+        all the samples, the feature pass and Renderer.denoise_variance
+        (**params as its)."""
         with Renderer(device=device, precision=precision) as r:
             r.set_accel(accel)
             r.set_scene(flatten(world, lights))
+            if variance:
+                spp = int(self.raw.samples_per_pixel)
+                sums, moments = r.render_window_moments(self, seed, 0, spp)
+                features, _ = r.render_features(self, seed, want_ids=False)
+                return r.denoise_variance(sums, features, moments, spp, **params)
             sums = r.render(self, seed)
             features, _ = r.render_features(self, seed, want_ids=False)
             return r.denoise(sums, features, int(self.raw.samples_per_pixel), **params)
@@ -675,6 +683,7 @@ class Renderer:
         self.device = device
         self.precision = precision
         self.stats = _capi.rtw_stats()
+        self._adaptive_size = None    # (W, H) of the last adaptive render: adaptive_moments
         self._listed = devices is not None or virtual_ranks is not None
 
     @property
@@ -767,6 +776,65 @@ class Renderer:
                        C.byref(self.stats)), name)
         return sums
 
+    def render_window_moments(self, cam: Camera, seed: int, first: int, n: int, sums=None, moments=None):
+        """render_window that also keeps each pixel's luminance moments
+        (rtw_render_window_moments): (sums float64 [H, W, 3], moments float64
+        [H, W, 2] = {sum Y, sum Y*Y}) of samples [0, first + n), continuing
+        `sums` and `moments` of samples [0, first) in place (neither is needed
+        when first == 0).  One sample per item: the sums are render_window's at
+        chunk 1 bit for bit, and windows compose bit for bit.  One-device
+        Renderers only."""
+        H, W = cam.raw.image_height, cam.raw.image_width
+        if sums is None or moments is None:
+            if first:
+                raise RenderError(_capi.RTW_E_INVALID, "render_window_moments: first > 0 continues `sums` and `moments`")
+            sums = np.zeros((H, W, 3), np.float64) if sums is None else sums
+            moments = np.zeros((H, W, 2), np.float64) if moments is None else moments
+        for a, k, what in ((sums, 3, "sums"), (moments, 2, "moments")):
+            if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.shape == (H, W, k)
+                    and a.flags.c_contiguous and a.flags.writeable):
+                raise RenderError(_capi.RTW_E_INVALID, f"{what} must be a contiguous float64 array [H, W, {k}]")
+        self._check(_lib.rtw_render_window_moments(self.ctx, C.byref(cam.raw), C.c_uint64(seed), first, n,
+                                                   sums.ctypes.data_as(_capi._f64p),
+                                                   moments.ctypes.data_as(_capi._f64p), C.byref(self.stats)),
+                    "rtw_render_window_moments")
+        return sums, moments
+
+    def render_window_moments_device(self, cam: Camera, seed: int, first: int, n: int, sums_ptr: int,
+                                     sums_bytes: int, moments_ptr: int, moments_bytes: int, *,
+                                     stream: int | None = None):
+        """render_window_moments on device memory (rtw_render_window_moments_device):
+        image-order H*W*3 float64 sums and H*W*2 float64 moments, continued in
+        place; on torch's current stream by default."""
+        if stream is None:
+            stream = _torch_stream(self.device)
+        self._check(_lib.rtw_render_window_moments_device(
+            self.ctx, C.byref(cam.raw), C.c_uint64(seed), first, n, C.c_void_p(sums_ptr) if sums_ptr else None,
+            sums_bytes, C.c_void_p(moments_ptr) if moments_ptr else None, moments_bytes,
+            C.c_void_p(stream) if stream else None), "rtw_render_window_moments_device")
+
+    def adaptive_moments(self, width: int | None = None, height: int | None = None) -> np.ndarray:
+        """The luminance moments float64 [H, W, 2] = {sum Y, sum Y*Y} of the
+        last render_adaptive / render_adaptive_device on this one-device
+        Renderer, over each pixel's first counts[pixel] samples
+        (rtw_adaptive_moments).  The image size is that render's."""
+        if width is None or height is None:
+            if self._adaptive_size is None:
+                raise RenderError(_capi.RTW_E_INVALID, "adaptive_moments: no adaptive render on this Renderer yet")
+            width, height = self._adaptive_size
+        moments = np.zeros((height, width, 2), np.float64)
+        self._check(_lib.rtw_adaptive_moments(self.ctx, moments.ctypes.data_as(_capi._f64p)), "rtw_adaptive_moments")
+        return moments
+
+    def adaptive_moments_device(self, moments_ptr: int, moments_bytes: int, *, stream: int | None = None):
+        """adaptive_moments into device memory (rtw_adaptive_moments_device):
+        H*W*2 float64, on torch's current stream by default."""
+        if stream is None:
+            stream = _torch_stream(self.device)
+        self._check(_lib.rtw_adaptive_moments_device(self.ctx, C.c_void_p(moments_ptr) if moments_ptr else None,
+                                                     moments_bytes, C.c_void_p(stream) if stream else None),
+                    "rtw_adaptive_moments_device")
+
     def render_window_device(self, cam: Camera, seed: int, first: int, n: int, accum_ptr: int,
                              accum_bytes: int, *, rank: int = 0, nranks: int = 1, stream: int | None = None):
         """Asynchronous window [first, first + n) of this rank's tiles folded
@@ -801,6 +869,7 @@ class Renderer:
         self._check(fn(self.ctx, C.byref(cam.raw), C.c_uint64(seed), min_samples, max_samples, window,
                        float(tolerance), sums.ctypes.data_as(_capi._f64p), counts.ctypes.data_as(_capi._u32p),
                        C.byref(self.stats)), name)
+        self._adaptive_size = (W, H)
         return sums, counts
 
     def render_adaptive_device(self, cam: Camera, seed: int, min_samples: int, max_samples: int, window: int,
@@ -820,6 +889,7 @@ class Renderer:
                        float(tolerance), C.c_void_p(sums_ptr) if sums_ptr else None, sums_bytes,
                        C.c_void_p(counts_ptr) if counts_ptr else None, counts_bytes,
                        C.c_void_p(stream) if stream else None), name)
+        self._adaptive_size = (int(cam.raw.image_width), int(cam.raw.image_height))
 
     def render_image_device(self, cam: Camera, seed: int, image_ptr: int, image_bytes: int, *,
                             stream: int | None = None):
@@ -1857,6 +1927,63 @@ class Renderer:
                                      out.ctypes.data_as(C.c_void_p)), "rtw_denoise")
         return out
 
+    # ---- the variance-guided denoiser (rtw_denoise_variance)
+    def denoise_variance(self, sums, features, moments, n, **params):
+        """The variance-guided a-trous filter of include/rtw.h: denoise's
+        inputs plus the luminance moments [H, W, 2] float64 of the same samples
+        (render_window_moments, adaptive_moments), whose per-pixel standard
+        error scales the colour stop.  Returns the filtered per-sample MEANS
+        [H, W, 3] float64.  Keyword parameters as DenoiseVarianceParams
+        (iterations, normal_power_log2, sigma_var, sigma_depth, demodulate,
+        fill_nonfinite).  numpy arrays go through the host entry; torch GPU
+        tensors -- float32 or float64 sums, float64 features and moments, int32
+        / uint32 counts -- through the device entry on torch's current stream,
+        and a torch tensor comes back."""
+        p = DenoiseVarianceParams(**params).raw
+        if type(sums).__module__.split(".")[0] == "torch":
+            import torch
+            H, W = int(sums.shape[0]), int(sums.shape[1])
+            per_pixel = type(n).__module__.split(".")[0] == "torch"
+            checks = [(sums, (torch.float32, torch.float64), (H, W, 3), "sums"),
+                      (features, (torch.float64,), (H, W, 8), "features"),
+                      (moments, (torch.float64,), (H, W, 2), "moments")]
+            if per_pixel:
+                checks.append((n, (torch.int32, getattr(torch, "uint32", torch.int32)), (H, W), "counts"))
+            for a, dts, shape, what in checks:
+                if not (type(a).__module__.split(".")[0] == "torch" and a.dtype in dts and a.is_cuda
+                        and a.device.index == self.device and a.is_contiguous() and tuple(a.shape) == shape):
+                    raise RenderError(_capi.RTW_E_INVALID, f"denoise_variance: {what} must be a contiguous "
+                                      f"{list(shape)} tensor of {dts} on device {self.device}")
+            out = torch.empty((H, W, 3), dtype=torch.float64, device=sums.device)
+            stream = _torch_stream(self.device)
+            self._check(_lib.rtw_denoise_variance_device(
+                self.ctx, C.c_void_p(sums.data_ptr()), RTW_F32 if sums.dtype == torch.float32 else RTW_F64,
+                sums.numel() * sums.element_size(), C.c_void_p(features.data_ptr()), features.numel() * 8,
+                C.c_void_p(moments.data_ptr()), moments.numel() * 8,
+                C.c_void_p(n.data_ptr()) if per_pixel else None, n.numel() * 4 if per_pixel else 0,
+                0 if per_pixel else int(n), W, H, C.byref(p), C.c_void_p(out.data_ptr()), out.numel() * 8,
+                C.c_void_p(stream) if stream else None), "rtw_denoise_variance_device")
+            return out
+        s = np.ascontiguousarray(np.asarray(sums), np.float64)
+        if s.ndim != 3 or s.shape[2] != 3:
+            raise RenderError(_capi.RTW_E_INVALID, f"denoise_variance: sums must be [H, W, 3], got {list(s.shape)}")
+        H, W = s.shape[:2]
+        f = np.ascontiguousarray(np.asarray(features), np.float64)
+        if f.shape != (H, W, 8):
+            raise RenderError(_capi.RTW_E_INVALID,
+                              f"denoise_variance: features must be {[H, W, 8]}, got {list(f.shape)}")
+        m = np.ascontiguousarray(np.asarray(moments), np.float64)
+        if m.shape != (H, W, 2):
+            raise RenderError(_capi.RTW_E_INVALID,
+                              f"denoise_variance: moments must be {[H, W, 2]}, got {list(m.shape)}")
+        cnt = _counts(n, H, W)
+        out = np.zeros((H, W, 3), np.float64)
+        self._check(_lib.rtw_denoise_variance(
+            self.ctx, s.ctypes.data_as(C.c_void_p), f.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p),
+            cnt.ctypes.data_as(C.c_void_p) if cnt is not None else None, 0 if cnt is not None else int(n), W, H,
+            C.byref(p), out.ctypes.data_as(C.c_void_p)), "rtw_denoise_variance")
+        return out
+
     def denoise_stats(self) -> "_capi.rtw_denoise_stats":
         """Counters of the last denoise (rtw_get_denoise_stats; waits for it):
         iterations, lds_iterations, filled, left_nonfinite, kernel_ms."""
@@ -2080,6 +2207,30 @@ class DenoiseParams:
         for k, v in fields.items():
             if k not in self.FIELDS:
                 raise RenderError(_capi.RTW_E_INVALID, f"DenoiseParams has no field {k!r} (it has {self.FIELDS})")
+            setattr(self.raw, k, float(v) if k.startswith("sigma") else int(v))
+
+    def __getattr__(self, name):
+        return getattr(self.__dict__["raw"], name)
+
+    def as_dict(self):
+        return {f: getattr(self.raw, f) for f in self.FIELDS}
+
+
+class DenoiseVarianceParams:
+    """rtw_denoise_variance_params: the library's defaults
+    (rtw_denoise_variance_params_default) with the given fields replaced --
+    iterations (1..16), normal_power_log2 (0..10), sigma_var (>= 0: the colour
+    stop's width in standard errors of the centre pixel), sigma_depth (> 0),
+    demodulate, fill_nonfinite (0 / 1).  The library checks the ranges."""
+    FIELDS = tuple(f for f, _ in _capi.rtw_denoise_variance_params._fields_)
+
+    def __init__(self, **fields):
+        self.raw = _capi.rtw_denoise_variance_params()
+        _lib.rtw_denoise_variance_params_default(C.byref(self.raw))
+        for k, v in fields.items():
+            if k not in self.FIELDS:
+                raise RenderError(_capi.RTW_E_INVALID,
+                                  f"DenoiseVarianceParams has no field {k!r} (it has {self.FIELDS})")
             setattr(self.raw, k, float(v) if k.startswith("sigma") else int(v))
 
     def __getattr__(self, name):

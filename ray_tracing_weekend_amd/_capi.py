@@ -101,6 +101,14 @@ class rtw_denoise_params(C.Structure):
     ]
 
 
+class rtw_denoise_variance_params(C.Structure):
+    _fields_ = [
+        ("iterations", C.c_uint32), ("normal_power_log2", C.c_uint32),
+        ("sigma_var", C.c_double), ("sigma_depth", C.c_double),
+        ("demodulate", C.c_uint32), ("fill_nonfinite", C.c_uint32),
+    ]
+
+
 class rtw_denoise_stats(C.Structure):
     _fields_ = [
         ("iterations", C.c_uint32), ("lds_iterations", C.c_uint32),
@@ -140,6 +148,13 @@ PROTOTYPES = [
                                            C.c_void_p]),
     ("rtw_render_window", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32, C.c_uint32,
                                     _f64p, C.POINTER(rtw_stats)]),
+    ("rtw_render_window_moments", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32, C.c_uint32,
+                                            _f64p, _f64p, C.POINTER(rtw_stats)]),
+    ("rtw_render_window_moments_device", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32,
+                                                   C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                   C.c_void_p]),
+    ("rtw_adaptive_moments", C.c_int, [C.c_void_p, _f64p]),
+    ("rtw_adaptive_moments_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("rtw_render_adaptive", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32, C.c_uint32,
                                       C.c_uint32, C.c_double, _f64p, _u32p, C.POINTER(rtw_stats)]),
     ("rtw_render_adaptive_device", C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint64, C.c_uint32,
@@ -232,6 +247,13 @@ PROTOTYPES = [
                                      C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.POINTER(rtw_denoise_params), C.c_void_p, C.c_size_t, C.c_void_p]),
     ("rtw_get_denoise_stats", C.c_int, [C.c_void_p, C.POINTER(rtw_denoise_stats)]),
+    ("rtw_denoise_variance_params_default", None, [C.POINTER(rtw_denoise_variance_params)]),
+    ("rtw_denoise_variance", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                       C.c_uint32, C.c_uint32, C.POINTER(rtw_denoise_variance_params), C.c_void_p]),
+    ("rtw_denoise_variance_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t,
+                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32,
+                                              C.c_uint32, C.c_uint32, C.POINTER(rtw_denoise_variance_params),
+                                              C.c_void_p, C.c_size_t, C.c_void_p]),
     ("rtw_scene_simple", C.c_void_p, [C.c_uint64, C.c_int]),
     ("rtw_world_scene", C.POINTER(rtw_scene), [C.c_void_p]),
     ("rtw_world_camera_builder", None, [C.c_void_p, C.POINTER(rtw_camera_builder)]),

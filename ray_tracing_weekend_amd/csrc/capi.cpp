@@ -51,6 +51,7 @@ void rtw_destroy(rtw_ctx* c) {
     if (c->d_accum) (void)hipFree(c->d_accum);
     if (c->d_adapt) (void)hipFree(c->d_adapt);
     if (c->d_adapt_img) (void)hipFree(c->d_adapt_img);
+    if (c->d_moments_img) (void)hipFree(c->d_moments_img);
     if (c->h_adapt) (void)hipHostFree(c->h_adapt);
     if (c->d_out) (void)hipFree(c->d_out);
     if (c->d_img) (void)hipFree(c->d_img);
@@ -183,6 +184,7 @@ static int upload_scene(rtw_ctx* c, const std::vector<unsigned char>& blob, rtw:
     HIP_TRY(c, hipMemcpy(c->d_scene, blob.data(), blob.size(), hipMemcpyHostToDevice));
     c->has_scene = true;
     ++c->scene_serial;
+    c->adapt_done = false;   // (rtw_adaptive_moments: the state is another scene's)
     return RTW_OK;
 }
 

@@ -177,6 +177,7 @@ int adaptive_end(AdaptiveRun& r) {
 template <typename R>
 int render_adaptive_t(rtw_ctx* c, const AdaptiveArgs& a, double* d_sums, uint32_t* d_counts, hipStream_t stream) {
     AdaptiveRun r;
+    c->adapt_done = false;   // (d_adapt is this render's from here on: rtw_adaptive_moments)
     int rc = adaptive_begin(r, c, a.cam, stream, nullptr);
     const uint32_t n_passes = rtw::adaptive_passes(a.min_samples, a.max_samples, a.window);
     for (uint32_t k = 0; k < n_passes && r.n_active && !rc; ++k) {
@@ -187,7 +188,12 @@ int render_adaptive_t(rtw_ctx* c, const AdaptiveArgs& a, double* d_sums, uint32_
     if (rtw::launch_unpack_adaptive(r.b.sums, r.b.counts, a.cam->image_width, a.cam->image_height, d_sums, d_counts,
                                     stream))
         return fail(c, RTW_E_DEVICE, std::string("adaptive unpack launch failed: ") + hipGetErrorString(hipGetLastError()));
-    return adaptive_end(r);
+    rc = adaptive_end(r);
+    if (rc) return rc;
+    c->adapt_done = true;
+    c->adapt_w = a.cam->image_width;
+    c->adapt_h = a.cam->image_height;
+    return RTW_OK;
 }
 
 // The passes of an n-rank render, in lockstep: rank k owns the tiles the

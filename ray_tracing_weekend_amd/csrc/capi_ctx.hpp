@@ -1,6 +1,7 @@
 // capi_ctx.hpp -- private to the C-ABI units (capi.cpp, capi_render.cpp,
 // capi_lpt.cpp, capi_adaptive.cpp, capi_multi.cpp, capi_query.cpp, capi_nee.cpp,
-// capi_path.cpp, capi_wavefront.cpp, capi_features.cpp, capi_denoise.cpp): the context behind include/rtw.h's rtw_ctx and the
+// capi_path.cpp, capi_wavefront.cpp, capi_features.cpp, capi_denoise.cpp, capi_denoise_variance.cpp,
+// capi_moments.cpp): the context behind include/rtw.h's rtw_ctx and the
 // helpers they share.
 #pragma once
 
@@ -117,10 +118,13 @@ struct QueryState {
     bool any = false;                 // a query was launched
 };
 
-// rtw_denoise (capi_denoise.cpp): the record arrays, the counters and events and
-// the host form's staging, allocated by the first denoise and grown on demand.
+// rtw_denoise (capi_denoise.cpp) and rtw_denoise_variance (capi_denoise_variance.cpp):
+// the record arrays, the counters and events and the host forms' staging, allocated by
+// the first denoise and grown on demand.
 struct DenoiseState {
-    void* d_records = nullptr;        // guide | albedo | colour 0 | colour 1 (host/denoise_plan.hpp)
+    // guide | albedo | colour 0 | colour 1 (host/denoise_plan.hpp), then the variance
+    // filter's variance 0 | variance 1 (host/denoise_variance_plan.hpp)
+    void* d_records = nullptr;
     size_t records_cap = 0;
     unsigned long long* d_counters = nullptr;   // {filled, left non-finite}
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -131,6 +135,8 @@ struct DenoiseState {
     size_t features_cap = 0;
     void* d_counts = nullptr;
     size_t counts_cap = 0;
+    void* d_moments = nullptr;        // (the variance filter's)
+    size_t moments_cap = 0;
     void* d_out = nullptr;
     size_t out_cap = 0;
     rtw_denoise_stats last{};
@@ -170,6 +176,13 @@ struct rtw_ctx {
     size_t adapt_cap = 0;
     void* d_adapt_img = nullptr;
     size_t adapt_img_cap = 0;
+    // d_adapt holds the whole state of a finished one-device adaptive render of this image
+    // size (rtw_adaptive_moments reads its {S1, S2}); rtw_set_scene forgets it
+    bool adapt_done = false;
+    uint32_t adapt_w = 0, adapt_h = 0;
+    // rtw_render_window_moments' host form: the image-order sums, then the moments
+    void* d_moments_img = nullptr;
+    size_t moments_img_cap = 0;
     // ... and two pinned host words: the {length, pixels} read back after each pass (a
     // copy into pageable memory could hold the host until the pass is done)
     uint32_t* h_adapt = nullptr;
@@ -340,3 +353,5 @@ void destroy_query(rtw_ctx* c);
 int query_state(rtw_ctx* c);
 // capi_denoise.cpp: rtw_destroy's part for the denoise state (the context's device is current)
 void destroy_denoise(rtw_ctx* c);
+// capi_denoise.cpp: the context's denoise state, allocated on first use
+int denoise_state(rtw_ctx* c);

@@ -18,14 +18,13 @@ void destroy_denoise(rtw_ctx* c) {
     if (d->d_sums) (void)hipFree(d->d_sums);
     if (d->d_features) (void)hipFree(d->d_features);
     if (d->d_counts) (void)hipFree(d->d_counts);
+    if (d->d_moments) (void)hipFree(d->d_moments);
     if (d->d_out) (void)hipFree(d->d_out);
     if (d->ev0) (void)hipEventDestroy(d->ev0);
     if (d->ev1) (void)hipEventDestroy(d->ev1);
     delete d;
     c->denoise = nullptr;
 }
-
-namespace {
 
 int denoise_state(rtw_ctx* c) {
     if (c->denoise) return RTW_OK;
@@ -37,6 +36,8 @@ int denoise_state(rtw_ctx* c) {
     HIP_TRY(c, hipEventCreate(&d->ev1));
     return RTW_OK;
 }
+
+namespace {
 
 // what both forms refuse before any device call; the plan of a call that can run
 int denoise_checks(rtw_ctx* c, const void* sums, const double* features, const uint32_t* counts, uint32_t spp,

@@ -4,7 +4,7 @@
 // writes image.ppm (P3, rows top to bottom).
 //
 //   rtw <scene> [--debug] [--seed N] [--f64] [--device N | --device-mask M] [--config PATH] [--out PATH]
-//       [--features PREFIX] [--denoise PATH]
+//       [--features PREFIX] [--denoise PATH [--denoise-variance]]
 //
 // --features PREFIX also writes the denoising guides of the render
 // (rtw_render_features, on one device): PREFIX_albedo.ppm, the albedo sums with
@@ -13,7 +13,10 @@
 //
 // --denoise PATH also writes the denoised image (rtw_denoise over the render's
 // sums and its feature pass, with the default parameters); it implies the
-// feature pass and runs on one device like --features.
+// feature pass and runs on one device like --features.  With --denoise-variance
+// the denoised image is the variance-guided filter's instead
+// (rtw_render_window_moments of all the samples, then rtw_denoise_variance with
+// the default parameters).
 //
 // <scene> is one of clap's ValueEnum names of main.rs:29-38 (cornell-box,
 // debug, checkered-spheres, perlin-spheres, plane, simple, simple-light,
@@ -64,6 +67,7 @@ bool read_config(const std::string& path, std::map<std::string, std::string>* kv
 
 int main(int argc, char** argv) {
     std::string scene, config = "Config.toml", out = "image.ppm", features, denoised;
+    bool variance = false;
     rtw::RenderOptions opt;
     for (int a = 1; a < argc; ++a) {
         std::string s = argv[a];
@@ -77,8 +81,13 @@ int main(int argc, char** argv) {
         else if (s == "--out" && a + 1 < argc) out = argv[++a];
         else if (s == "--features" && a + 1 < argc) features = argv[++a];
         else if (s == "--denoise" && a + 1 < argc) denoised = argv[++a];
+        else if (s == "--denoise-variance") variance = true;
         else if (scene.empty()) scene = s;
         else { fprintf(stderr, "unexpected argument %s\n", s.c_str()); return 2; }
+    }
+    if (variance && denoised.empty()) {
+        fprintf(stderr, "--denoise-variance goes with --denoise PATH\n");
+        return 2;
     }
     for (char& ch : scene)
         if (ch == '-') ch = '_';
@@ -147,7 +156,14 @@ int main(int argc, char** argv) {
             const std::vector<double> f = cam.render_features(world, lights, 0, spp, {}, nullptr, fopt);
             if (!denoised.empty()) {
                 rtw_denoise_stats st{};
-                const std::vector<double> mean = rtw::denoise(sums, f, {}, spp, W, H, nullptr, &st, fopt);
+                std::vector<double> mean;
+                if (variance) {
+                    std::vector<double> wsums, moments;
+                    cam.render_window_moments(world, lights, 0, spp, wsums, moments, fopt);
+                    mean = rtw::denoise_variance(wsums, f, moments, {}, spp, W, H, nullptr, &st, fopt);
+                } else {
+                    mean = rtw::denoise(sums, f, {}, spp, W, H, nullptr, &st, fopt);
+                }
                 if (rtw_write_ppm(denoised.c_str(), mean.data(), W, H, 1) < 0) {
                     fprintf(stderr, "cannot write %s\n", denoised.c_str());
                     return 1;

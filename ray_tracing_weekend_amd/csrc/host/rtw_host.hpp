@@ -265,6 +265,14 @@ class Camera {
     std::vector<double> render_features(const HittableList& world, const HittableList& lights, uint32_t first = 0,
                                         uint32_t n = 0, const std::vector<uint32_t>& counts = {},
                                         std::vector<int32_t>* ids = nullptr, const RenderOptions& opt = {}) const;
+    // The samples [first, first + n) of every pixel with their luminance moments
+    // (rtw_render_window_moments, include/rtw.h; one device, one sample per item):
+    // sums [H][W][3] and moments [H][W][2] = {sum Y, sum Y*Y} are continued in
+    // place, and start from zero when first is 0.  samples_per_pixel is not read.
+    // Defined in host/denoise_variance.cpp.
+    void render_window_moments(const HittableList& world, const HittableList& lights, uint32_t first, uint32_t n,
+                               std::vector<double>& sums, std::vector<double>& moments,
+                               const RenderOptions& opt = {}) const;
     const rtw_camera& raw() const { return c_; }
 
    private:
@@ -390,6 +398,14 @@ std::vector<double> denoise(const std::vector<double>& sums, const std::vector<d
                             const std::vector<uint32_t>& counts, uint32_t spp, uint32_t width, uint32_t height,
                             const rtw_denoise_params* params = nullptr, rtw_denoise_stats* stats = nullptr,
                             const RenderOptions& opt = {});
+// The variance-guided denoiser (rtw_denoise_variance, include/rtw.h): denoise's
+// arguments and the luminance moments [H][W][2] of the same samples
+// (Camera::render_window_moments).  Defined in host/denoise_variance.cpp.
+std::vector<double> denoise_variance(const std::vector<double>& sums, const std::vector<double>& features,
+                                     const std::vector<double>& moments, const std::vector<uint32_t>& counts,
+                                     uint32_t spp, uint32_t width, uint32_t height,
+                                     const rtw_denoise_variance_params* params = nullptr,
+                                     rtw_denoise_stats* stats = nullptr, const RenderOptions& opt = {});
 
 namespace scenes {
 // scenes::simple restated with the build's seeded RNG; grid a, b in [-n, n).

@@ -24,8 +24,17 @@ not depend on the precision), depth 50.
            sample counts: the RMS after the filter, which picks the defaults.
   kernels  `rocprofv3 --kernel-trace --stats` around one `pass` process, a run of
            its own: the time of each denoise kernel.
+  vpass    the variance-guided filter (rtw_denoise_variance_device) next to the old
+           one in one process, alternating, on the sums and moments of one
+           rtw_render_window_moments_device call: both passes' times, and the
+           quality of the old filter and of the new one at sigma_var {1, 1.5, 2,
+           3, 4} against the same reference.
+  vab      `ab` for the variance-guided filter: it stages up to step 4.
+  moments  rtw_render_window_moments against rtw_render_window, the workload's
+           samples in one window, alternating rounds of one process (kernel_ms of
+           the render stats: the render kernel and its folds).
 
-    python tools/denoise_bench.py [--what pass,ab,sweep,kernels] [--repeats 5] [--ref-spp 2000] [--out FILE]
+    python tools/denoise_bench.py [--what pass,ab,sweep,kernels,vpass,vab,moments] [--repeats 5] [--ref-spp 2000] [--out FILE]
     python tools/denoise_bench.py --one KIND --workload NAME:WxH:SPP ...   (internal: one measurement)
 """
 import argparse
@@ -187,6 +196,122 @@ def one_sweep(workload, ref_path):
           flush=True)
 
 
+SIGMA_VARS = (1.0, 1.5, 2.0, 3.0, 4.0)
+
+
+def moments_inputs(rtw, r, cam, spp):
+    """(d_sums, d_moments, d_features) of the workload on the device, one moments window."""
+    import torch
+    h, w = cam.image_height, cam.image_width
+    d_sums = torch.zeros((h, w, 3), dtype=torch.float64, device="cuda:0")
+    d_mom = torch.zeros((h, w, 2), dtype=torch.float64, device="cuda:0")
+    r.render_window_moments_device(cam, SEED, 0, spp, d_sums.data_ptr(), d_sums.numel() * 8, d_mom.data_ptr(),
+                                   d_mom.numel() * 8)
+    d_feat = torch.zeros((h, w, 8), dtype=torch.float64, device="cuda:0")
+    r.render_features(cam, SEED, features=d_feat, want_ids=False)
+    torch.cuda.synchronize()
+    return d_sums, d_mom, d_feat
+
+
+def one_vpass(workload, repeats, ref_path):
+    import numpy as np
+    rtw, scene, cam = setup(workload)
+    name, w, h, spp = parse(workload)
+    with rtw.Renderer(device=0, precision=rtw.RTW_F64) as r:
+        r.set_scene(scene)
+        d_sums, d_mom, d_feat = moments_inputs(rtw, r, cam, spp)
+        t = {"old": [], "new": []}
+        for rep in range(1 + repeats):                  # rep 0: warm-up; the two filters alternate
+            for which in ("old", "new") if rep % 2 else ("new", "old"):
+                if which == "old":
+                    old = r.denoise(d_sums, d_feat, spp)
+                else:
+                    new = r.denoise_variance(d_sums, d_feat, d_mom, spp)
+                st = r.denoise_stats()
+                if rep:
+                    t[which].append(st.kernel_ms)
+                if which == "new":
+                    lds_new = int(st.lds_iterations)
+        old_ms, old_spread = med(t["old"])
+        new_ms, new_spread = med(t["new"])
+        line = {"what": "vpass", "workload": workload, "old_params": rtw.DenoiseParams().as_dict(),
+                "new_params": rtw.DenoiseVarianceParams().as_dict(), "old_ms": old_ms, "old_ms_spread": old_spread,
+                "new_ms": new_ms, "new_ms_spread": new_spread, "new_over_old": round(new_ms / old_ms, 3),
+                "new_lds_iterations": lds_new}
+        if ref_path:
+            ref = np.load(ref_path)
+            noisy = d_sums.cpu().numpy() / spp
+            ok = np.isfinite(noisy).all(-1) & np.isfinite(ref).all(-1)
+            old_mean = old.cpu().numpy()
+            line.update({"nonfinite_in": int((~np.isfinite(noisy).all(-1)).sum()),
+                         "rms_noisy": round(rms(noisy, ref, ok), 6),
+                         "rms_old": round(rms(old_mean, ref, ok & np.isfinite(old_mean).all(-1)), 6), "rms_new": {}})
+            for sv in SIGMA_VARS:
+                mean = r.denoise_variance(d_sums, d_feat, d_mom, spp, sigma_var=sv).cpu().numpy()
+                line["rms_new"][str(sv)] = round(rms(mean, ref, ok & np.isfinite(mean).all(-1)), 6)
+                line["left_nonfinite"] = int(r.denoise_stats().left_nonfinite)
+        del new
+    print(json.dumps(line), flush=True)
+
+
+def one_vab(workload, repeats):
+    rtw, scene, cam = setup(workload)
+    name, w, h, spp = parse(workload)
+    with rtw.Renderer(device=0, precision=rtw.RTW_F64) as r0, rtw.Renderer(device=0, precision=rtw.RTW_F64) as r2:
+        r0.set_scene(scene)
+        r0.set_tuning("denoise_lds", 0)
+        r2.set_tuning("denoise_lds", 2)
+        d_sums, d_mom, d_feat = moments_inputs(rtw, r0, cam, spp)
+        t = {(lds, it): [] for lds in (0, 2) for it in range(1, 6)}
+        staged = {}
+        for rep in range(1 + repeats):                  # rep 0: warm-up; the two forms alternate
+            for it in range(1, 6):
+                for lds, r in ((0, r0), (2, r2)) if rep % 2 else ((2, r2), (0, r0)):
+                    r.denoise_variance(d_sums, d_feat, d_mom, spp, iterations=it)
+                    st = r.denoise_stats()
+                    staged[(lds, it)] = int(st.lds_iterations)
+                    if rep:
+                        t[(lds, it)].append(st.kernel_ms)
+    line = {"what": "vab", "workload": workload, "steps": []}
+    prev = {0: 0.0, 2: 0.0}
+    for it in range(1, 6):
+        m0, s0 = med(t[(0, it)])
+        m2, s2 = med(t[(2, it)])
+        line["steps"].append({"step": 1 << (it - 1), "staged_with_lds_2": staged[(2, it)] == it,
+                              "pass_direct_ms": m0, "pass_direct_spread": s0, "pass_lds_ms": m2, "pass_lds_spread": s2,
+                              "step_direct_ms": round(m0 - prev[0], 4), "step_lds_ms": round(m2 - prev[2], 4)})
+        prev = {0: m0, 2: m2}
+    print(json.dumps(line), flush=True)
+
+
+def one_moments(workload, repeats):
+    """rtw_render_window_moments against rtw_render_window: one window of the workload's samples."""
+    import numpy as np
+    rtw, scene, cam = setup(workload)
+    name, w, h, spp = parse(workload)
+    t = {"window": [], "moments": []}
+    chunk = {}
+    with rtw.Renderer(device=0, precision=rtw.RTW_F64) as r:
+        r.set_scene(scene)
+        sums, msums, moments = np.zeros((h, w, 3)), np.zeros((h, w, 3)), np.zeros((h, w, 2))
+        for rep in range(1 + repeats):                  # rep 0: warm-up; the two entries alternate
+            for which in ("window", "moments") if rep % 2 else ("moments", "window"):
+                if which == "window":
+                    r.render_window(cam, SEED, 0, spp, sums)
+                else:
+                    r.render_window_moments(cam, SEED, 0, spp, msums, moments)
+                chunk[which] = int(r.stats.chunk)
+                if rep:
+                    t[which].append(float(r.stats.kernel_ms))
+    wm, ws = med(t["window"])
+    mm, ms = med(t["moments"])
+    same = bool(np.all((sums == msums) | (np.isnan(sums) & np.isnan(msums))))
+    print(json.dumps({"what": "moments", "workload": workload, "window_ms": wm, "window_ms_spread": ws,
+                      "window_chunk": chunk["window"], "moments_ms": mm, "moments_ms_spread": ms,
+                      "moments_over_window": round(mm / wm, 4), "difference_ms": round(mm - wm, 3),
+                      "same_sums": same}), flush=True)
+
+
 def kernels(workload, repeats):
     """rocprofv3 --kernel-trace --stats around one `pass` process: the denoise kernels' rows."""
     with tempfile.TemporaryDirectory() as d:
@@ -230,6 +355,12 @@ def main():
         return one_ab(a.workload, a.repeats)
     if a.one == "sweep":
         return one_sweep(a.workload, a.ref)
+    if a.one == "vpass":
+        return one_vpass(a.workload, a.repeats, a.ref)
+    if a.one == "vab":
+        return one_vab(a.workload, a.repeats)
+    if a.one == "moments":
+        return one_moments(a.workload, a.repeats)
     what, lines = a.what.split(","), []
 
     def child(*args):
@@ -246,7 +377,7 @@ def main():
         for wl in a.workloads.split(","):
             name, w, h, spp = parse(wl)
             key = f"{name}_{w}x{h}"
-            if key not in refs and ("pass" in what or "sweep" in what):
+            if key not in refs and ("pass" in what or "sweep" in what or "vpass" in what):
                 refs[key] = os.path.join(d, key + ".npy")
                 subprocess.run([sys.executable, os.path.abspath(__file__), "--one", "reference", "--workload", wl,
                                 "--ref", refs[key], "--ref-spp", str(a.ref_spp)], check=True, timeout=900)
@@ -257,6 +388,12 @@ def main():
                 child("--one", "ab", "--workload", wl, "--repeats", str(2 * a.repeats))
             if "sweep" in what and spp <= 64:
                 child("--one", "sweep", "--workload", wl, "--ref", refs[key])
+            if "vpass" in what:
+                child("--one", "vpass", "--workload", wl, "--repeats", str(a.repeats), "--ref", refs[key])
+            if "vab" in what and spp == 64:
+                child("--one", "vab", "--workload", wl, "--repeats", str(2 * a.repeats))
+            if "moments" in what and spp == 500:
+                child("--one", "moments", "--workload", wl, "--repeats", str(a.repeats))
             if "kernels" in what and spp == 64:
                 line = kernels(wl, a.repeats)
                 if line is None:
